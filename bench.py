@@ -28,6 +28,14 @@ processes, before anything touches a GPU: launch_ranks) unless a launcher
 reference scales its hashing with cores the same way, one worker per core
 (processor.go:401-408, HashWorkers = runtime.NumCPU()).
 
+A plain run sets up, runs --warmup steps and the pre-warm, times --steps steps
+(value, ms_per_step and the dominant kernel's roofline come from that region),
+writes the last step's outputs if --dump-outputs is given, and prints the line.
+--full adds every other leg, as before it existed: the host-API / cgo /
+multi-device calls, the other kernels' timing pass, repeated regions,
+overlapped cycles, the clock probe, the self-check against the oracle, the
+config-3 leg and the CPU baselines; a plain run reports those as null.
+
 Prints ONE JSON line (rank 0).
 """
 from __future__ import annotations
@@ -94,6 +102,17 @@ def parse():
     p.add_argument("--launch-check", action="store_true",
                    help="launcher plumbing only (CPU tests): ranks rendezvous over gloo, barrier, gather their "
                         "request ranges, rank 0 prints the line with value null; no device, no hashing")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline, also run every other leg: the PCIe-inclusive host API, the cgo path and "
+                        "the multi-device call (before the steps), the other kernels' timing pass, the repeated "
+                        "regions, the overlapped cycles, the clock probe, the self-check against the oracle, the "
+                        "config-3 leg and the CPU baselines (each still has its own switch below); a plain run "
+                        "sets up, warms up, times --steps steps and prints the line with those fields null")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed (the digests a caller "
+                        "receives) as DIR/<name>.npy, float32, one value per digest byte; an output larger than "
+                        "its share of DUMP_BUDGET_BYTES is written as a fixed, seeded sample of its rows "
+                        "(sample_rows); ranks of a multi-GPU run write DIR/<name>.rank<r>.npy")
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=100,
                    help="untimed steps; MI355X needs ~20+ ms of sustained load to reach its working clock")
@@ -236,6 +255,45 @@ def event_steps(steps, every):
     return [i for i in range(steps) if i % every == every - 1]
 
 
+DUMP_BUDGET_BYTES = 48_000_000  # --dump-outputs: all files of one rank together (float32), under 64 MB
+DUMP_SEED = 0x64756D70
+
+
+def sample_rows(n_rows, row_bytes, budget, seed=DUMP_SEED):
+    """Rows of an (n_rows, ...) output that --dump-outputs writes: None (all of
+    them) when n_rows x row_bytes fits `budget`, else budget // row_bytes
+    distinct rows, ascending, drawn by a fixed seed -- the same rows in every
+    run and every build, the first and the last row always among them."""
+    keep = int(budget) // int(row_bytes)
+    if n_rows <= keep:
+        return None
+    rng = np.random.default_rng(seed)
+    rows = rng.choice(n_rows, size=max(keep, 2), replace=False)
+    rows[:2] = (0, n_rows - 1)
+    return np.unique(rows).astype(np.int64)
+
+
+def snapshot_outputs(outputs, budget=DUMP_BUDGET_BYTES):
+    """Copies of a step's outputs ({name: (n, 32) uint8 digests, a device tensor
+    or a host array}) cut to sample_rows, taken right behind the timed region:
+    later legs of a --full run reuse the buffers."""
+    snap = {}
+    for name, arr in outputs.items():
+        rows = sample_rows(arr.shape[0], 4 * int(np.prod(arr.shape[1:])), budget // max(len(outputs), 1))
+        if isinstance(arr, np.ndarray):
+            snap[name] = arr.copy() if rows is None else arr[rows]
+        else:
+            snap[name] = arr.clone() if rows is None else arr.index_select(0, torch.from_numpy(rows).to(arr.device))
+    return snap
+
+
+def write_outputs(out_dir, snap, rank=0, world=1):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in snap.items():
+        host = arr if isinstance(arr, np.ndarray) else arr.cpu().numpy()
+        np.save(os.path.join(out_dir, name + (f".rank{rank}" if world > 1 else "") + ".npy"), host.astype(np.float32))
+
+
 def check_windows(n_batches, batch_size, seed, per_window=256):
     """Batch ranges [b0, b1) the self-check samples: the first window, the
     last (it ends with the final batch, which is short when BatchSize does not
@@ -325,6 +383,10 @@ class BatchWorkload:
     def after(self):
         if self.plan is not None:
             self.plan.status()  # raises if a fused run's readiness watchdog ever expired
+
+    def outputs(self):
+        """What the last step left for its caller (--dump-outputs)."""
+        return {"request_digests": self.d_req, "batch_digests": self.d_bat}
 
     def dominant(self):
         """(kernel name, launches, ms, compressions, algorithmic HBM bytes) of the dominant kernel."""
@@ -652,7 +714,8 @@ class BatchWorkload:
         mode = self.plan.mode_name if self.plan is not None else "none"
         if self.overlap:
             return {"batch_pass": "overlapped: the previous cycle's batch chains in each cycle's request launch"}
-        return {"batch_kernel_avg_ms": getattr(self, "batch_ms_timed", 0.0) / self.a.steps,
+        bt = getattr(self, "batch_ms_timed", None)  # None: a plain run has no pass over the other kernels
+        return {"batch_kernel_avg_ms": None if bt is None else bt / self.a.steps,
                 "batch_pass": {"none": "sequential batch kernel (plain device API)",
                                "fused": "fused into the request launch (readiness counters, no second kernel)",
                                "sequential": "plan: request kernel then batch kernel"}[mode],
@@ -720,6 +783,9 @@ class MixedWorkload:
 
     def after(self):
         pass
+
+    def outputs(self):
+        return {"request_digests": self.d_req}
 
     def dominant(self):
         n_m, ms_m = self.eng.kernel_time(KERNEL_MSGS)
@@ -801,10 +867,13 @@ class EpochChangeWorkload:
         eng.set_stream(None)  # host API on the engine's own stream
 
     def step(self):
-        self.eng.hash_slice_arrays(self.sl, dedup=self.dedup)
+        self.out = self.eng.hash_slice_arrays(self.sl, dedup=self.dedup)
 
     def after(self):
         pass
+
+    def outputs(self):
+        return {"request_digests": self.out}
 
     def dominant(self):
         n_m, ms_m = self.eng.kernel_time(KERNEL_MSGS)
@@ -924,6 +993,8 @@ def small_cycle_bench(a, eng):
                      "submit_wait_us": asyn[0], "submit_wait_p90_us": asyn[1],
                      "cpu_1core_us": cpu[0], "cpu_1core_p90_us": cpu[1]})
     last = rows[-1]
+    if a.dump_outputs:  # the largest cycle's digests: one more synchronous call on the same slices
+        write_outputs(a.dump_outputs, {"digests": eng.hash_slice_arrays(arrays)})
     print(json.dumps({
         "metric": "Ready()-cycle hash latency, small testengine cycles (BASELINE config 1 shape)",
         "value": last["hash_requests"] / (last["hash_slices_us"] * 1e-6), "unit": "digests/s",
@@ -940,7 +1011,7 @@ def small_cycle_bench(a, eng):
 
 def config3_leg(a, eng, dev):
     """BASELINE config 3 (2^18 x 4 KB requests + VerifyBatch-500 digests) as a
-    leg of the default run, after config 2's timed region and self-check
+    leg of the --full run, after config 2's timed region and self-check
     (rank 0, N = 1): the fused plan's step (request + VerifyBatch chains in
     one launch, readiness counters), its dominant-kernel time and roofline
     fraction, the overlapped-cycles figure on the same plan, the sequential
@@ -1215,12 +1286,13 @@ def main():
         wl = {4: EpochChangeWorkload}.get(a.config, BatchWorkload)(a, eng, dev, rank)
     torch.cuda.synchronize(dev)
 
-    # PCIe-inclusive host-API rate (rank 0, N=1 only), measured before the
-    # device-resident steps.
-    pcie = wl.pcie() if rank == 0 and world == 1 and not a.no_pcie else None
-    cgo = wl.cgo_path() if rank == 0 and world == 1 and not a.no_pcie and hasattr(wl, "cgo_path") else None
+    # --full only: the PCIe-inclusive host-API rate (rank 0, N=1 only),
+    # measured before the device-resident steps.
+    host_legs = a.full and rank == 0 and world == 1 and not a.no_pcie
+    pcie = wl.pcie() if host_legs else None
+    cgo = wl.cgo_path() if host_legs and hasattr(wl, "cgo_path") else None
     multi = None
-    if rank == 0 and world == 1 and not a.no_pcie and a.config == 2 and hasattr(wl, "multi_device"):
+    if host_legs and a.config == 2 and hasattr(wl, "multi_device"):
         try:  # an extra leg: a failure is reported in the line, not fatal to it
             multi = wl.multi_device()
         except Exception as e:  # noqa: BLE001
@@ -1271,29 +1343,34 @@ def main():
         timed(True)
     wl.after()
     kname, n_k, ms_k, work_blocks, hbm_bytes = wl.dominant()
-    if a.timed_kernels == "dominant":
+    # --dump-outputs: the last timed step's outputs, copied on the device now
+    # (the legs of a --full run write the same buffers) and saved before the line.
+    snap = snapshot_outputs(wl.outputs()) if a.dump_outputs else None
+    # Everything from here to the line's arithmetic is --full only: a plain
+    # run has timed its steps and reports those legs as null.
+    if a.full and a.timed_kernels == "dominant":
         # Second-pass timing of the other kernels (batch kernel figures in the
         # line's extras); the value and the roofline come from the pass above.
         eng.set_timing_mask(range(32))
         timed(True)
     # Batch-pass kernel time of the last timing pass, read before
     # overlap_cycles() resets the engine's timers.
-    if hasattr(wl, "batch_ms"):
+    if hasattr(wl, "batch_ms") and (a.full or a.timed_kernels == "all"):
         wl.batch_ms_timed = wl.batch_ms()
     # SURVEY.md §8d asks for a median over repeats: the same timed region
     # --repeat-regions more times, bare (no events), each bracketed like the
     # headline's; reported beside the value, never as it.
-    rep_ms = [timed(False) / a.steps * 1e3 for _ in range(max(0, a.repeat_regions))]
+    rep_ms = [timed(False) / a.steps * 1e3 for _ in range(max(0, a.repeat_regions) if a.full else 0)]
 
     # Configs 2/3 with a sequential plan: the overlapped-cycles figure, right
     # behind the timed region too (the chip still at its load clock).
-    if rank == 0 and a.overlap_extra and hasattr(wl, "overlap_cycles"):
+    if a.full and rank == 0 and a.overlap_extra and hasattr(wl, "overlap_cycles"):
         wl.ovl = wl.overlap_cycles()
 
     # Clock probe right behind the timed region (chip still at its load clock):
     # register-only compressions in the request kernel's round form.
     probe = None
-    if a.probe_iters > 0:
+    if a.full and a.probe_iters > 0:
         ghz, cyc = eng.clock_probe(a.probe_iters)
         probe = {"clock_ghz": ghz, "cycles_per_wave_compression": cyc}
 
@@ -1306,8 +1383,9 @@ def main():
     # Every rank checks the last step of its OWN request range against the CPU
     # oracle on samples (first / last / random requests and the batches over
     # them, the final partial batch included); the line's self_check is the
-    # AND over ranks, each rank's own is in per_rank.
-    check_ok = bool(wl.self_check())
+    # AND over ranks, each rank's own is in per_rank.  --full only (null in a
+    # plain run, whose outputs --dump-outputs hands to the caller instead).
+    check_ok = bool(wl.self_check()) if a.full else None
 
     # Whole-job totals: the sum over ranks (config 5's block-balanced shards
     # differ in request count per rank).  step_compressions = every
@@ -1340,13 +1418,13 @@ def main():
                     "note": "clock probe: 8 waves/SIMD of register-only compressions (the request kernel's "
                             "round form), right after the timed region"}
 
-    # Config 3 (the north_star's 4 KB target) as a leg of the default run.
+    # Config 3 (the north_star's 4 KB target) as a leg of the --full run.
     c3 = None
-    if rank == 0 and world == 1 and a.config == 2 and a.config3_leg and a.requests == 0:
+    if a.full and rank == 0 and world == 1 and a.config == 2 and a.config3_leg and a.requests == 0:
         eng.set_stream(stream.cuda_stream)
         c3 = config3_leg(a, eng, dev)
 
-    cpu = wl.cpu_baseline(a.cpu_seconds) if rank == 0 and world == 1 and a.cpu_seconds > 0 else None
+    cpu = wl.cpu_baseline(a.cpu_seconds) if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0 else None
 
     # Per-rank evidence (control plane, after the timed region): which device
     # each rank ran on and its own dominant-kernel time, so a multi-GPU line
@@ -1362,7 +1440,9 @@ def main():
     if dist:
         per_rank = [None] * world
         dist.all_gather_object(per_rank, rank_info)
-    check_all = all(p["self_check"] for p in per_rank)
+    check_all = all(p["self_check"] for p in per_rank) if a.full else None
+    if snap is not None:
+        write_outputs(a.dump_outputs, snap, rank, world)
     ident = device_identity_check(per_rank, rehearsal)
     if ident["distinct"] is False:
         raise SystemExit(f"bench.py: rank {rank}: ranks share a device ({ident['note']}); a multi-GPU line "
@@ -1429,9 +1509,15 @@ def main():
                                 "note": "the same timed region again, bare, max over ranks not taken; the value "
                                         "is the first region's"} if rep_ms else None),
             "timed_kernels": a.timed_kernels,
+            "full": bool(a.full),
+            "dump_outputs": ({"dir": a.dump_outputs, "files": sorted(snap), "dtype": "float32",
+                              "note": "the last timed step's digests, one value per byte; an output over its share "
+                                      "of the budget is a fixed seeded sample of rows (sample_rows)"}
+                             if snap is not None else None),
             "self_check": check_all,
-            "self_check_scope": "every rank: its own range's first and last batch-aligned windows (the final "
-                                "partial batch included) and 4 random ones, request + batch digests vs the oracle",
+            "self_check_scope": ("every rank: its own range's first and last batch-aligned windows (the final "
+                                 "partial batch included) and 4 random ones, request + batch digests vs the oracle"
+                                 if a.full else "not run: --full only"),
             "per_rank": per_rank,
             "distributed": {"world_size": world, "backend": backend if dist else None,
                             "device_identity": ident,

@@ -1,9 +1,10 @@
 #!/bin/bash
 # rocprofv3 passes over the driver's own bench command (run on the GPU box from
 # the repo root):
-#   1. kernel trace + stats of exactly `bench.py --gpus 1 --steps 20 --warmup 5`
-#      (plus any extra args): per-kernel average duration, to agree with the
-#      bench line's HIP-event kernel time;
+#   1. kernel trace + stats of `bench.py --gpus 1 --steps 20 --warmup 5 --full`
+#      (plus any extra args; --full: every leg and kernel, as the command ran
+#      before the option existed): per-kernel average duration, to agree with
+#      the bench line's HIP-event kernel time;
 #   2..n. one --pmc pass each (counters never combined with other trace
 #      domains), same command without the CPU baseline / PCIe legs.
 # Usage: profiles/profile.sh <tag> [extra bench args...]
@@ -14,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 TAG=${1:-r02}
 shift || true
-ARGS=("--gpus" "1" "--steps" "20" "--warmup" "5" "$@")
+ARGS=("--gpus" "1" "--steps" "20" "--warmup" "5" "--full" "$@")
 PARGS=("${ARGS[@]}" "--cpu-seconds" "0" "--no-pcie" "--no-config3-leg")
 OUT=gpurun_out/prof_${TAG}
 mkdir -p "$OUT"

@@ -114,6 +114,44 @@ def test_evp_pool_on_config2_sample():
     assert np.array_equal(o.evp_hash_requests(arena, off, ln, threads=8), o.hash_requests(arena, off, ln))
 
 
+def test_sample_rows_fixed_and_within_budget():
+    assert bench.sample_rows(1000, 128, 128_000) is None  # fits: every row
+    rows = bench.sample_rows(1 << 20, 128, 24_000_000)
+    assert rows.size <= 24_000_000 // 128 and rows.size > 0.99 * (24_000_000 // 128)
+    assert rows[0] == 0 and rows[-1] == (1 << 20) - 1 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(rows, bench.sample_rows(1 << 20, 128, 24_000_000))  # the same rows every run
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs on host arrays (config 4's shape of output): float32
+    files, a sampled output next to a whole one, all under the budget."""
+    rng = np.random.default_rng(3)
+    req = rng.integers(0, 256, (5000, 32), dtype=np.uint8)
+    bat = rng.integers(0, 256, (250, 32), dtype=np.uint8)
+    snap = bench.snapshot_outputs({"request_digests": req, "batch_digests": bat}, budget=2 * 128 * 1000)
+    req[:] = 0  # the snapshot is a copy: later legs reuse the buffers
+    bat[:] = 0
+    bench.write_outputs(str(tmp_path / "d"), snap)
+    r, b = np.load(tmp_path / "d" / "request_digests.npy"), np.load(tmp_path / "d" / "batch_digests.npy")
+    assert r.dtype == b.dtype == np.float32 and b.shape == (250, 32) and r.shape[1] == 32 and 990 <= r.shape[0] <= 1000
+    rows = bench.sample_rows(5000, 128, 128 * 1000)
+    want = np.random.default_rng(3).integers(0, 256, (5000, 32), dtype=np.uint8)
+    assert np.array_equal(r, want[rows].astype(np.float32))
+    assert r.nbytes + b.nbytes <= 2 * 128 * 1000
+    bench.write_outputs(str(tmp_path / "d"), snap, rank=1, world=2)
+    assert (tmp_path / "d" / "request_digests.rank1.npy").exists()
+    assert bench.DUMP_BUDGET_BYTES <= 64_000_000 - 4096
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "x"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "x"
+
+
 @pytest.mark.parametrize("steps,every,want", [(20, 4, [3, 7, 11, 15, 19]), (20, 1, list(range(20))),
                                               (5, 4, [3]), (3, 4, [2]), (1, 4, [0]), (50, 4, list(range(3, 50, 4)))])
 def test_event_steps_sample_every_kth_never_the_first(steps, every, want):

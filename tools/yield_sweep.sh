@@ -31,7 +31,7 @@ mkdir -p "$OUT"
 for rep in 1 2; do
     for f in "${FORMS[@]}"; do
         MIRSHA_AB=1 MIRSHA_PROBE_WAVES=4 MIRSHA_AB_LIB=tools/ablib/y$f/libmirsha.so timeout -k 10 120 \
-            python3 bench.py --config 3 --pipeline sequential --steps 40 --warmup 10 --no-pcie --cpu-seconds 0 \
+            python3 bench.py --full --config 3 --pipeline sequential --steps 40 --warmup 10 --no-pcie --cpu-seconds 0 \
             --no-overlap-extra --probe-iters 64 > "$OUT/y${f}_$rep.json" 2> "$OUT/y${f}_$rep.err"
         echo "$f $rep done"
     done
