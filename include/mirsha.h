@@ -100,7 +100,7 @@ int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
  * kernel: 0 = message kernel, 1 = digest-list (batch) kernel, 2 = generator
  * and clock probe, 3 = batch-chain kernel, 4 = fused request -> batch kernel
  * (one persistent launch per run), 5 = overlapped-cycles kernel
- * (mirsha_pipeline_overlap_device).
+ * (mirsha_pipeline_overlap_device), 6 = digest compare kernel (mirsha_verify_*).
  * set_timing_mask: bit k on = kernel k is timed while timing is enabled
  * (default: all). */
 int mirsha_ctx_set_timing(mirsha_ctx* ctx, int enable);
@@ -256,7 +256,50 @@ int mirsha_digest_lists(mirsha_ctx* ctx, const uint8_t* digests, uint32_t n_dige
                         const uint32_t* idx, const uint32_t* list_first, uint32_t n_lists,
                         uint8_t* digests_out);
 
+/* ------------------------------------------------------ verify on the device */
+/* Two hash origins carry the digest they expect: VerifyRequest compares with
+ * RequestAck.Digest (state_machine.go:408-417), VerifyBatch with
+ * ExpectedDigest (batch_tracker.go:139-174); a mismatch is the protocol's
+ * byzantine signal.  These calls hash as their mirsha_hash_* counterparts do
+ * (same arguments, checks, error codes and messages, `expected` standing
+ * where the digest output stood), keep the digests on the device, compare
+ * them there and return only a verdict:
+ *   expected        exactly 32 bytes per item (a caller holding an expectation
+ *                   of another length has a mismatch without asking: Go's
+ *                   bytes.Equal) -- travels H2D with the call;
+ *   bits_out        ceil(n / 64) words, bit i & 63 of word i >> 6 set exactly
+ *                   when item i's digest differs from expected[32 i ..] in any
+ *                   bit; bits at or beyond n are 0; may be NULL when only the
+ *                   count is wanted;
+ *   *n_mismatch_out number of set bits.
+ * Synchronous.  No digest crosses PCIe: a call moves 8 + 8 ceil(n / 64) bytes
+ * device -> host (count, bitmap), where the hash call moves 32 n.  Both
+ * staging routes are covered (single-shot; pipelined above 32 MiB of request
+ * bytes, one compare behind the last chunk).  mirsha_ctx_host_profile keeps
+ * its phases; scatter = the verdict's copy to the caller. */
+int mirsha_verify_slices(mirsha_ctx* ctx, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                         const uint32_t* slice_first, uint32_t n, const uint8_t* expected,
+                         uint64_t* bits_out, uint32_t* n_mismatch_out);
+int mirsha_verify_batch(mirsha_ctx* ctx, const uint8_t* arena, uint64_t arena_len,
+                        const uint64_t* off, const uint32_t* len, uint32_t n, const uint8_t* expected,
+                        uint64_t* bits_out, uint32_t* n_mismatch_out);
+/* mirsha_digest_lists' arguments (MIRSHA_NULL_INDEX entries, empty lists), one
+ * expected digest per list: the VerifyBatch flow (batch_tracker.go:147-150). */
+int mirsha_verify_digest_lists(mirsha_ctx* ctx, const uint8_t* digests, uint32_t n_digests,
+                               const uint32_t* idx, const uint32_t* list_first, uint32_t n_lists,
+                               const uint8_t* expected, uint64_t* bits_out, uint32_t* n_mismatch_out);
+
 /* -------------------------------------------------------------- device API */
+/* Compare of n device-resident 32-byte digests with n expected ones; device
+ * pointers, asynchronous on the context stream.  Every word of the
+ * ceil(n / 64)-word bitmap is written (layout as bits_out above) and
+ * *d_count_out is reset by the call itself before the mismatches are added,
+ * so repeated calls do not accumulate.  n == 0: the count is written as 0 and
+ * no kernel is launched.  d_digests and d_expected must be 16-byte aligned,
+ * d_bits_out 8-byte aligned (else MIRSHA_EINVAL, nothing is launched). */
+int mirsha_verify_digests_device(mirsha_ctx* ctx, const uint8_t* d_digests, const uint8_t* d_expected,
+                                 uint32_t n, uint64_t* d_bits_out, uint32_t* d_count_out);
+
 /* All pointers are device pointers; asynchronous on the context stream.
  * Reads past arena_len return 0.  Any arena size: up to
  * MIRSHA_MAX_DEVICE_ARENA_BYTES one 32-bit buffer descriptor addresses it,

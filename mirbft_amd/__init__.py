@@ -8,7 +8,7 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
 from .engine import (CheckpointChains, Engine, MultiEngine, SliceArrays, Ticket, bucket_order, dedup_plan, device_count,
-                     hash_batch_multi)
+                     hash_batch_multi, mismatch_indices)
 from .processor import (ActionResults, Actions, GpuHash, HashRequest, HashResult, PendingResults, Processor,
                         ProcessorWorkPool, gpu_hasher)
 
@@ -25,6 +25,7 @@ __all__ = [
     "device_count",
     "hash_batch_multi",
     "MultiEngine",
+    "mismatch_indices",
     "eventlog",
     "hashdata",
     "sharding",

@@ -66,6 +66,19 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p],
     ),
     "mirsha_digest_lists": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "mirsha_verify_slices": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, _u32p],
+    ),
+    "mirsha_verify_batch": (
+        c_int,
+        [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, _u32p],
+    ),
+    "mirsha_verify_digest_lists": (
+        c_int,
+        [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, _u32p],
+    ),
+    "mirsha_verify_digests_device": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
     "mirsha_hash_batch_device": (
         c_int,
         [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p],

@@ -1,5 +1,6 @@
 // mirsha_api.hip — host side of the C-ABI declared in include/mirsha.h:
-// contexts, timing, the device-pointer API, synthetic streams, streaming
+// contexts, timing, the device-pointer API (the digest compare of
+// mirsha_verify_* among it), synthetic streams, streaming
 // checkpoint chains and the clock probe.  The other host units are listed in
 // mirsha_ctx.h.
 #include "mirsha_ctx.h"
@@ -88,11 +89,20 @@ int check_lists(mirsha_ctx* c, const uint32_t* idx, const uint32_t* first, uint3
     return MIRSHA_OK;
 }
 
+int queue_verify(mirsha_ctx* c, const uint8_t* d_digests, const uint8_t* d_expected, uint32_t n, uint64_t* d_bits,
+                 uint32_t* d_count) {
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(uint32_t), c->stream));
+    if (n == 0) return MIRSHA_OK;
+    return timed_launch(c, kTimerVerify, [&] {
+        return mirsha::launch_verify_digests(d_digests, d_expected, n, d_bits, d_count, c->stream);
+    });
+}
+
 }  // namespace mirsha_api
 
 extern "C" {
 
-int mirsha_version(void) { return (0 << 16) | 1; }
+int mirsha_version(void) { return (0 << 16) | 2; }
 
 int mirsha_device_count(int* count) {
     if (!count) return MIRSHA_EINVAL;
@@ -148,6 +158,7 @@ void mirsha_ctx_destroy(mirsha_ctx* c) {
     c->h_meta.release();
     c->h_outs.release();
     c->d_meta.release();
+    c->h_expect.release(); c->h_verdict.release(); c->d_expect.release(); c->d_verdict.release();
     for (auto e : c->xev) (void)hipEventDestroy(e);
     if (c->xin) (void)hipStreamDestroy(c->xin);
     if (c->xout) (void)hipStreamDestroy(c->xout);
@@ -184,7 +195,7 @@ int mirsha_ctx_set_timing(mirsha_ctx* c, int enable) {
 }
 
 int mirsha_ctx_kernel_time(mirsha_ctx* c, int which, uint64_t* launches, double* total_ms) {
-    if (!c || which < 0 || which > 5) return MIRSHA_EINVAL;
+    if (!c || which < 0 || which >= kKernelTimers) return MIRSHA_EINVAL;
     if (int rc = use_device(c)) return rc;
     KernelTimer& t = c->timers[which];
     for (auto& pr : t.pending) {
@@ -210,7 +221,7 @@ int mirsha_ctx_set_timing_mask(mirsha_ctx* c, uint32_t mask) {
 
 int mirsha_ctx_reset_timing(mirsha_ctx* c) {
     if (!c) return MIRSHA_EINVAL;
-    for (int k = 0; k < 6; k++) {
+    for (int k = 0; k < kKernelTimers; k++) {
         int rc = mirsha_ctx_kernel_time(c, k, nullptr, nullptr);
         if (rc) return rc;
         c->timers[k].launches = 0;
@@ -264,6 +275,19 @@ int mirsha_digest_lists_device(mirsha_ctx* c, const uint8_t* d_digests, uint32_t
         return mirsha::launch_lists(d_digests, n_digests, d_idx, n_entries, d_first, n_lists,
                                     c->d_scratch.as<uint32_t>(), d_out, c->stream);
     });
+}
+
+int mirsha_verify_digests_device(mirsha_ctx* c, const uint8_t* d_digests, const uint8_t* d_expected, uint32_t n,
+                                 uint64_t* d_bits_out, uint32_t* d_count_out) {
+    if (!c) return MIRSHA_EINVAL;
+    if (!d_count_out) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (n && (!d_digests || !d_expected || !d_bits_out)) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (n && (((uintptr_t)d_digests | (uintptr_t)d_expected) & 15u))
+        return fail(c, MIRSHA_EINVAL, "digest arrays must be 16-byte aligned");
+    if (n && ((uintptr_t)d_bits_out & 7u)) return fail(c, MIRSHA_EINVAL, "bitmap must be 8-byte aligned");
+    if ((uintptr_t)d_count_out & 3u) return fail(c, MIRSHA_EINVAL, "count must be 4-byte aligned");
+    if (int rc = use_device(c)) return rc;
+    return queue_verify(c, d_digests, d_expected, n, d_bits_out, d_count_out);
 }
 
 int mirsha_bucket_order(const uint32_t* len, uint32_t n, uint32_t* order_out) {

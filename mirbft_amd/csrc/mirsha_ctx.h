@@ -5,7 +5,9 @@
 //                       streams, checkpoint chains, clock probe
 //   mirsha_staging.hip  synchronous host calls: staging, pipelined H2D /
 //                       kernels / D2H (mirsha_hash_batch / _slices /
-//                       _requests_then_batches, mirsha_digest_lists)
+//                       _requests_then_batches, mirsha_digest_lists) and their
+//                       verify forms (mirsha_verify_batch / _slices /
+//                       _digest_lists: compare on the device, verdict back)
 //   mirsha_plan.hip     request -> batch plans: sequential, fused (placement
 //                       probe), overlapped cycles (mirsha_pipeline_*)
 //   mirsha_async.hip    the asynchronous ring (mirsha_submit_* / wait / poll,
@@ -129,6 +131,9 @@ struct AsyncSlot {
     double prof[MIRSHA_PROF_PHASES] = {};  // this submission's host phases (published when it completes)
 };
 
+constexpr int kKernelTimers = 7;  // timing ids 0-6 (mirsha.h, mirsha_ctx_kernel_time)
+constexpr int kTimerVerify = 6;
+
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     std::vector<hipEvent_t> pool;
@@ -167,7 +172,12 @@ struct mirsha_ctx {
     // and zeroing per 2^20 requests.
     std::vector<uint32_t> sl_len;
     std::vector<uint64_t> sl_poff;
-    KernelTimer timers[6];         // msgs, lists, gen, chain, fused, overlap
+    KernelTimer timers[kKernelTimers];  // msgs, lists, gen, chain, fused, overlap, verify
+    // Verify calls (mirsha_verify_*): the expected digests (pinned staging of a
+    // pageable caller array, device copy) and the verdict block
+    // [count u32, pad | bitmap u64[ceil(n/64)]] on the device and pinned.
+    PinnedBuf h_expect, h_verdict;
+    DevBuf d_expect, d_verdict;
     AsyncSlot slots[kAsyncSlots];
     uint64_t next_ticket = 1;  // ticket of the next submission
     uint64_t done_ticket = 0;  // every ticket <= this one has completed
@@ -271,6 +281,13 @@ bool bucket_order(const uint32_t* len, uint32_t n, uint32_t* order);
 
 int check_lists(mirsha_ctx* c, const uint32_t* idx, const uint32_t* first, uint32_t n_lists, uint32_t n_digests);
 
+// Queues the device compare of n digests on c->stream: the count word is
+// reset (a memset on the stream), then verify_digests_kernel (timing id 6)
+// writes every word of the bitmap and adds up the mismatches.  n == 0: the
+// reset only.
+int queue_verify(mirsha_ctx* c, const uint8_t* d_digests, const uint8_t* d_expected, uint32_t n, uint64_t* d_bits,
+                 uint32_t* d_count);
+
 // A boolean A/B or diagnostic knob ("1" = set; only with MIRSHA_AB=1).
 inline bool getenv_flag(const char* name) {
     const char* e = mirsha::ab_getenv(name);
@@ -315,14 +332,23 @@ struct ArenaSrc {
 // starts at or after the previous one's end), which the pipelined form needs;
 // kGapless = in order with no gaps (off[i] - shift = len[0] + ... + len[i-1]).
 enum ArenaLayout { kAnyOrder = 0, kInOrder = 1, kGapless = 2 };
+// A verify call (mirsha_verify_*): the staged call keeps its digests on the
+// device, compares them there with `expected` (32 bytes each: the n request
+// digests, or with lists the n_lists list digests) and brings back only the
+// verdict; req_out / list_out are unused (NULL).
+struct VerifyArgs {
+    const uint8_t* expected = nullptr;
+    uint64_t* bits_out = nullptr;  // ceil(count / 64) words, or NULL
+    uint32_t* n_mismatch_out = nullptr;
+};
 int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const uint32_t* len, uint32_t n,
                uint64_t shift, ArenaLayout layout, const uint32_t* idx, const uint32_t* first, uint32_t n_lists,
-               uint8_t* req_out, uint8_t* list_out);
+               uint8_t* req_out, uint8_t* list_out, const VerifyArgs* verify = nullptr);
 int arena_span(mirsha_ctx* c, uint64_t arena_len, const uint64_t* off, const uint32_t* len, uint32_t n,
                uint64_t* lo_out, uint64_t* hi_out, uint64_t* total_out = nullptr, ArenaLayout* layout_out = nullptr);
 int run_arena_call(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, const uint64_t* off, const uint32_t* len,
                    uint32_t n, const uint32_t* idx, const uint32_t* first, uint32_t n_lists, uint8_t* req_out,
-                   uint8_t* list_out);
+                   uint8_t* list_out, const VerifyArgs* verify = nullptr);
 int slice_errors(mirsha_ctx* c, const uint8_t* err, uint32_t n);
 int slice_args(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len, const uint32_t* slice_first,
                uint32_t n, const uint8_t* out);

@@ -234,6 +234,12 @@ hipError_t launch_chains_absorb(const uint8_t* digests, const uint32_t* pos, con
 hipError_t launch_chains_sum(const uint32_t* which, uint32_t k, const uint32_t* h, const uint32_t* pend,
                              const uint64_t* cnt, uint8_t* out, hipStream_t s);
 hipError_t launch_chains_reset(const uint32_t* which, uint32_t k, uint32_t* h, uint64_t* cnt, hipStream_t s);
+// Mismatch bitmap of n 32-byte digests against n expected ones (both 16-byte
+// aligned): bit i & 63 of bits[i >> 6] = digest i differs; every word of the
+// ceil(n / 64)-word bitmap is written; *count += mismatches (the caller
+// resets it on the stream first).
+hipError_t launch_verify_digests(const uint8_t* digests, const uint8_t* expected, uint32_t n, uint64_t* bits,
+                                 uint32_t* count, hipStream_t s);
 hipError_t launch_gen_requests(uint64_t seed, uint64_t first, uint64_t count, uint32_t data_len,
                                uint8_t* arena, hipStream_t s);
 hipError_t launch_mixed_lengths(uint64_t seed, uint64_t first, uint64_t count, uint32_t* len, hipStream_t s);

@@ -2552,4 +2552,41 @@ hipError_t launch_gen_requests(uint64_t seed, uint64_t first, uint64_t count, ui
     return hipGetLastError();
 }
 
+// ---- digest verification ----------------------------------------------------
+// VerifyRequest / VerifyBatch (state_machine.go:408-417, batch_tracker.go:139-174)
+// compare a digest with the one the origin expects; here for a whole call, on
+// the device, so that only a verdict crosses PCIe.  One lane per digest: two
+// 128-bit loads from each array, XOR / OR reduce, one 64-bit ballot per wave.
+// Lane 0 of a wave stores the wave's word of the bitmap (lanes at or beyond n
+// vote 0 and issue no loads), and a wave with mismatches adds their number to
+// *count with one atomic.  Waves of the last workgroup that start at or beyond
+// n have no word and do nothing.
+__global__ __launch_bounds__(kBlockThreads) void verify_digests_kernel(const uint4* __restrict__ got,
+                                                                       const uint4* __restrict__ want, uint32_t n,
+                                                                       unsigned long long* __restrict__ bits,
+                                                                       uint32_t* __restrict__ count) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+    bool differs = false;
+    if (i < n) {
+        const uint4 a0 = got[2u * i], a1 = got[2u * i + 1u];
+        const uint4 b0 = want[2u * i], b1 = want[2u * i + 1u];
+        differs = (((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w)) |
+                   ((a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w))) != 0u;
+    }
+    const unsigned long long mask = __ballot(differs);
+    if ((threadIdx.x & 63u) == 0u && i < n) {
+        bits[i >> 6] = mask;
+        if (mask) atomicAdd(count, (uint32_t)__popcll(mask));
+    }
+}
+
+hipError_t launch_verify_digests(const uint8_t* digests, const uint8_t* expected, uint32_t n, uint64_t* bits,
+                                 uint32_t* count, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = (uint32_t)(((uint64_t)n + kBlockThreads - 1u) / kBlockThreads);
+    launch_k(verify_digests_kernel, grid, kBlockThreads, 0, s, reinterpret_cast<const uint4*>(digests),
+             reinterpret_cast<const uint4*>(expected), n, reinterpret_cast<unsigned long long*>(bits), count);
+    return hipGetLastError();
+}
+
 }  // namespace mirsha

@@ -1,7 +1,8 @@
 // mirsha_staging.hip — the synchronous host API (the Go drop-in's path: one
 // call per Ready() cycle): staging, the pipelined H2D / kernel / D2H form,
 // slice validation, and mirsha_hash_batch / _slices /
-// _requests_then_batches, mirsha_digest_lists.
+// _requests_then_batches, mirsha_digest_lists, mirsha_verify_batch / _slices /
+// _digest_lists.
 #include "mirsha_ctx.h"
 
 namespace mirsha_api {
@@ -160,6 +161,49 @@ hipError_t take_events(mirsha_ctx* c, size_t k) {
     return hipSuccess;
 }
 
+// ---- verify calls -------------------------------------------------------------
+// A verify call is its hash call with another ending: the digests stay in
+// d_out, the caller's expected digests go H2D beside the request bytes, one
+// compare kernel runs behind the last hashing kernel and ONE D2H brings back
+// the verdict block (8 bytes of count + 8 bytes per 64 digests).  No digest
+// crosses to the host.
+constexpr uint64_t kVerdictBits = 8;  // [count u32, pad u32 | bitmap words]
+inline uint64_t verdict_bytes(uint32_t count) { return kVerdictBits + 8ull * (((uint64_t)count + 63u) / 64u); }
+
+// Queues the expected digests' H2D on c->stream (straight from a page-locked
+// caller array, else through pinned staging) and sizes the verdict buffers.
+int verify_upload(mirsha_ctx* c, const VerifyArgs& v, uint32_t count) {
+    const uint64_t bytes = 32ull * count;
+    HIP_TRY(c, c->d_expect.ensure(std::max<uint64_t>(bytes, 32)));
+    HIP_TRY(c, c->d_verdict.ensure(verdict_bytes(count)));
+    HIP_TRY(c, c->h_verdict.ensure(verdict_bytes(count)));
+    const uint8_t* from = v.expected;
+    if (!host_pinned(from)) {
+        HIP_TRY(c, c->h_expect.ensure(std::max<uint64_t>(bytes, 32)));
+        pmemcpy(c->h_expect.p, v.expected, bytes);
+        from = c->h_expect.as<uint8_t>();
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_expect.p, from, bytes, hipMemcpyHostToDevice, c->stream));
+    return MIRSHA_OK;
+}
+
+// Behind the hashing kernels on c->stream: the compare and the verdict's D2H.
+int verify_queue(mirsha_ctx* c, const uint8_t* d_digests, uint32_t count) {
+    uint8_t* dv = c->d_verdict.as<uint8_t>();
+    if (int rc = queue_verify(c, d_digests, c->d_expect.as<uint8_t>(), count, reinterpret_cast<uint64_t*>(dv + kVerdictBits),
+                              reinterpret_cast<uint32_t*>(dv)))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->h_verdict.p, dv, verdict_bytes(count), hipMemcpyDeviceToHost, c->stream));
+    return MIRSHA_OK;
+}
+
+// After c->stream is synchronised: the verdict to the caller.
+void verify_publish(mirsha_ctx* c, const VerifyArgs& v, uint32_t count) {
+    const uint8_t* hv = c->h_verdict.as<uint8_t>();
+    if (v.bits_out) memcpy(v.bits_out, hv + kVerdictBits, verdict_bytes(count) - kVerdictBits);
+    memcpy(v.n_mismatch_out, hv, sizeof(uint32_t));
+}
+
 // The pipelined form of a large synchronous call (messages packed in order
 // in [0, total)).  The arena goes over PCIe in kStageChunk chunks on the xin
 // stream (straight from a page-locked caller arena, else packed by the host
@@ -202,7 +246,10 @@ struct PipeLayout {
 constexpr uint64_t kFirstChunk = 8ull << 20;
 int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const uint32_t* len, uint32_t n,
                   uint64_t shift, bool gapless, const uint32_t* idx, const uint32_t* first, uint32_t n_lists,
-                  uint8_t* req_out, uint8_t* list_out) {
+                  uint8_t* req_out, uint8_t* list_out, const VerifyArgs* verify) {
+    // A verify call keeps every chunk's digests in d_out and compares them
+    // all behind the last kernel: no per-chunk D2H, no copy-out.
+    const uint32_t n_verify = n_lists ? n_lists : n;
     double t_pack = 0.0, t_wait = 0.0, t_out = 0.0;
     // MIRSHA_STAGE_TRACE=1: one line per call on stderr with the host time
     // (us since entry) at which each chunk was queued and each wait returned.
@@ -333,6 +380,8 @@ int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const
         HIP_TRY(c, mirsha::launch_offsets_scan(c->d_scan.p, tb, reinterpret_cast<const uint32_t*>(dm + L.len),
                                                reinterpret_cast<uint64_t*>(dm + L.off), n, c->stream));
     }
+    if (verify)
+        if (int rc = verify_upload(c, *verify, n_verify)) return rc;
     c->prof[MIRSHA_PROF_PLAN] = ms_since(tp);
     mark("meta", 0);
 
@@ -341,13 +390,13 @@ int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const
     uint8_t* d_req = c->d_out.as<uint8_t>();
     uint8_t* d_lst = d_req + 32ull * n;
     const bool direct_out = host_pinned(req_out);
-    HIP_TRY(c, c->h_outs.ensure(std::max<uint64_t>(direct_out ? 32ull * n_lists : out_bytes, 32)));
+    HIP_TRY(c, c->h_outs.ensure(std::max<uint64_t>(verify ? 0 : direct_out ? 32ull * n_lists : out_bytes, 32)));
     uint8_t* h_req = direct_out ? req_out : c->h_outs.as<uint8_t>();
     uint8_t* h_lst = direct_out ? c->h_outs.as<uint8_t>() : h_req + 32ull * n;
 
     uint32_t copied = 0;  // chunks whose digests are in req_out
     auto copy_out = [&](uint32_t k0, uint32_t k1) {  // chunks [k0, k1), one parallel copy
-        if (!direct_out && cut[k1] > cut[k0]) {
+        if (!verify && !direct_out && cut[k1] > cut[k0]) {
             const auto w = Clock::now();
             pmemcpy(req_out + 32ull * cut[k0], h_req + 32ull * cut[k0], 32ull * (cut[k1] - cut[k0]));
             t_out += ms_since(w);
@@ -369,7 +418,8 @@ int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const
         }
         HIP_TRY(c, hipEventRecord(ev_kern[k], c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->xout, ev_kern[k], 0));
-        if (cnt) HIP_TRY(c, hipMemcpyAsync(h_req + 32ull * i0, d_req + 32ull * i0, 32ull * cnt, hipMemcpyDeviceToHost, c->xout));
+        if (cnt && !verify)
+            HIP_TRY(c, hipMemcpyAsync(h_req + 32ull * i0, d_req + 32ull * i0, 32ull * cnt, hipMemcpyDeviceToHost, c->xout));
         HIP_TRY(c, hipEventRecord(ev_out[k], c->xout));
         // digests that are already back go to the caller while later chunks pack
         uint32_t ready = copied;
@@ -395,9 +445,11 @@ int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const
             return rc;
         HIP_TRY(c, hipEventRecord(ev_lk, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->xout, ev_lk, 0));
-        HIP_TRY(c, hipMemcpyAsync(h_lst, d_lst, 32ull * n_lists, hipMemcpyDeviceToHost, c->xout));
+        if (!verify) HIP_TRY(c, hipMemcpyAsync(h_lst, d_lst, 32ull * n_lists, hipMemcpyDeviceToHost, c->xout));
         HIP_TRY(c, hipEventRecord(ev_lo, c->xout));
     }
+    if (verify)
+        if (int rc = verify_queue(c, n_lists ? d_lst : d_req, n_verify)) return rc;
     // The rest as it comes back: wait for the next chunk, copy it together
     // with every later chunk already back, while the remaining DMA runs.
     while (copied < nch) {
@@ -422,7 +474,15 @@ int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const
         const auto w = Clock::now();
         HIP_TRY(c, hipEventSynchronize(ev_lo));
         t_wait += ms_since(w);
-        memcpy(list_out, h_lst, 32ull * n_lists);
+        if (!verify) memcpy(list_out, h_lst, 32ull * n_lists);
+    }
+    if (verify) {
+        auto w = Clock::now();
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        t_wait += ms_since(w);
+        w = Clock::now();
+        verify_publish(c, *verify, n_verify);
+        t_out += ms_since(w);
     }
     mark("end", nch);
     if (trace) fprintf(stderr, "mirsha stage trace: %u chunks%s\n", nch, tl.c_str());
@@ -459,11 +519,12 @@ constexpr uint32_t kPipeMaxBlocks = 256;
 
 int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const uint32_t* len, uint32_t n,
                uint64_t shift, ArenaLayout layout, const uint32_t* idx, const uint32_t* first, uint32_t n_lists,
-               uint8_t* req_out, uint8_t* list_out) {
+               uint8_t* req_out, uint8_t* list_out, const VerifyArgs* verify) {
     if (n && layout != kAnyOrder && src.total > kStageChunk && !getenv_flag("MIRSHA_NO_PIPELINED_CALLS") &&
         max_blocks(len, n) <= kPipeMaxBlocks)
         return run_pipelined(c, src, off, len, n, shift, layout == kGapless && !getenv_flag("MIRSHA_NO_OFFSET_SCAN"),
-                             idx, first, n_lists, req_out, list_out);
+                             idx, first, n_lists, req_out, list_out, verify);
+    const uint32_t n_verify = n_lists ? n_lists : n;
     // Host phases into c->prof (mirsha_ctx_host_profile): pack = queueing the
     // request bytes, plan = metadata block, device = queue -> sync, scatter =
     // digests to the caller.  (validate is filled by the caller.)
@@ -493,6 +554,8 @@ int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const ui
     // and writing pinned digests over PCIe -- measured no faster: 47.6 vs
     // 44.5 us for a 17-request cycle, profiles/r02j.)
     HIP_TRY(c, hipMemcpyAsync(c->d_meta.p, h, L.end, hipMemcpyHostToDevice, c->stream));
+    if (verify)
+        if (int rc = verify_upload(c, *verify, n_verify)) return rc;
     uint8_t* dm = c->d_meta.as<uint8_t>();
     const uint8_t* d_arena = inl ? dm + L.arena : c->d_arena.as<uint8_t>();
     // Digests: requests then lists, contiguous (one D2H).
@@ -522,7 +585,13 @@ int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const ui
             }))
             return rc;
     }
-    if (out_bytes <= kPinnedOutMax) {
+    if (verify) {  // the compare behind the kernels; only the verdict comes back
+        if (int rc = verify_queue(c, n_lists ? d_lst : d_req, n_verify)) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->prof[MIRSHA_PROF_DEVICE] = ms_since(t0);
+        t0 = Clock::now();
+        verify_publish(c, *verify, n_verify);
+    } else if (out_bytes <= kPinnedOutMax) {
         HIP_TRY(c, c->h_outs.ensure(std::max<uint64_t>(out_bytes, 32)));
         HIP_TRY(c, hipMemcpyAsync(c->h_outs.p, d_req, out_bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -600,7 +669,7 @@ int arena_span(mirsha_ctx* c, uint64_t arena_len, const uint64_t* off, const uin
 // packed back to back (sparse arenas do not ship their gaps).
 int run_arena_call(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, const uint64_t* off, const uint32_t* len,
                    uint32_t n, const uint32_t* idx, const uint32_t* first, uint32_t n_lists, uint8_t* req_out,
-                   uint8_t* list_out) {
+                   uint8_t* list_out, const VerifyArgs* verify) {
     const auto t0 = Clock::now();
     for (double& x : c->prof) x = 0.0;
     uint64_t lo = 0, hi = 0, total = 0;
@@ -611,7 +680,7 @@ int run_arena_call(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, cons
     if (hi - lo <= 2 * total + 4096) {  // dense: ship the span, offsets rebased on lo
         src.base = arena + lo;
         src.total = hi - lo;
-        const int rc = run_staged(c, src, off, len, n, lo, layout, idx, first, n_lists, req_out, list_out);
+        const int rc = run_staged(c, src, off, len, n, lo, layout, idx, first, n_lists, req_out, list_out, verify);
         c->prof[MIRSHA_PROF_TOTAL] = ms_since(t0);
         return rc;
     }
@@ -635,7 +704,8 @@ int run_arena_call(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, cons
     src.poff = roff.data();
     src.n = n;
     src.total = total;
-    const int rc = run_staged(c, src, roff.data(), len, n, 0, kGapless, idx, first, n_lists, req_out, list_out);
+    const int rc =
+        run_staged(c, src, roff.data(), len, n, 0, kGapless, idx, first, n_lists, req_out, list_out, verify);
     c->prof[MIRSHA_PROF_TOTAL] = ms_since(t0);
     return rc;
 }
@@ -823,6 +893,69 @@ int mirsha_digest_lists(mirsha_ctx* c, const uint8_t* digests, uint32_t n_digest
     src.base = digests;
     src.total = 32ull * n_digests;
     return run_staged(c, src, nullptr, nullptr, 0, 0, kAnyOrder, idx, first, n_lists, nullptr, out);
+}
+
+// ---- verify calls: the hash calls above with the compare on the device --------
+// (`expected` stands where the hash call has its digest output: the same
+// checks, codes and messages.)
+
+int mirsha_verify_batch(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
+                        const uint32_t* len, uint32_t n, const uint8_t* expected, uint64_t* bits_out,
+                        uint32_t* n_mismatch_out) {
+    if (!c) return MIRSHA_EINVAL;
+    if (!n_mismatch_out) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    *n_mismatch_out = 0;
+    if (n == 0) return MIRSHA_OK;
+    if (!off || !len || !expected || (!arena && arena_len)) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (int rc = use_device(c)) return rc;
+    const VerifyArgs v{expected, bits_out, n_mismatch_out};
+    return run_arena_call(c, arena, arena_len, off, len, n, nullptr, nullptr, 0, nullptr, nullptr, &v);
+}
+
+int mirsha_verify_slices(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                         const uint32_t* slice_first, uint32_t n, const uint8_t* expected, uint64_t* bits_out,
+                         uint32_t* n_mismatch_out) {
+    if (!c) return MIRSHA_EINVAL;
+    if (!n_mismatch_out) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    *n_mismatch_out = 0;
+    if (n == 0) return MIRSHA_OK;
+    const auto t0 = Clock::now();
+    for (double& x : c->prof) x = 0.0;
+    std::vector<uint32_t>& len = c->sl_len;
+    if (int rc = slice_lengths(c, slice_ptr, slice_len, slice_first, n, expected, len)) return rc;
+    c->prof[MIRSHA_PROF_VALIDATE] = ms_since(t0);
+    if (int rc = use_device(c)) return rc;
+    std::vector<uint64_t>& poff = c->sl_poff;
+    if (poff.size() < n) poff.resize(n);
+    const uint64_t p = mirsha::host::exclusive_scan(len.data(), n, poff.data());
+    ArenaSrc src;
+    src.ptr = slice_ptr;
+    src.slen = slice_len;
+    src.sfirst = slice_first;
+    src.poff = poff.data();
+    src.n = n;
+    src.total = p;
+    const VerifyArgs v{expected, bits_out, n_mismatch_out};
+    const int rc = run_staged(c, src, poff.data(), len.data(), n, 0, kGapless, nullptr, nullptr, 0, nullptr, nullptr, &v);
+    c->prof[MIRSHA_PROF_TOTAL] = ms_since(t0);
+    return rc;
+}
+
+int mirsha_verify_digest_lists(mirsha_ctx* c, const uint8_t* digests, uint32_t n_digests, const uint32_t* idx,
+                               const uint32_t* first, uint32_t n_lists, const uint8_t* expected, uint64_t* bits_out,
+                               uint32_t* n_mismatch_out) {
+    if (!c) return MIRSHA_EINVAL;
+    if (!n_mismatch_out) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    *n_mismatch_out = 0;
+    if (n_lists == 0) return MIRSHA_OK;
+    if (!expected || (n_digests && !digests)) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (int rc = check_lists(c, idx, first, n_lists, n_digests)) return rc;
+    if (int rc = use_device(c)) return rc;
+    ArenaSrc src;
+    src.base = digests;
+    src.total = 32ull * n_digests;
+    const VerifyArgs v{expected, bits_out, n_mismatch_out};
+    return run_staged(c, src, nullptr, nullptr, 0, 0, kAnyOrder, idx, first, n_lists, nullptr, nullptr, &v);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@ KERNEL_GEN = 2
 KERNEL_CHAIN = 3
 KERNEL_FUSED = 4
 KERNEL_OVERLAP = 5
+KERNEL_VERIFY = 6
 ASYNC_SLOTS = 4  # submissions in flight per context (mirsha_submit_slices)
 
 # mirsha_pipeline modes (include/mirsha.h)
@@ -106,6 +107,38 @@ def _out_rows(out, n: int) -> np.ndarray:
             or not out.flags.writeable:
         raise ValueError(f"out must be a writeable C-contiguous uint8 array of shape ({n}, 32)")
     return out
+
+
+def mismatch_indices(bits, n: int) -> np.ndarray:
+    """Sorted indices of the set bits of a mismatch bitmap (mirsha_verify_*):
+    bit ``i & 63`` of word ``i >> 6`` is item ``i``; only the first n bits count."""
+    n = int(n)
+    words = np.ascontiguousarray(bits, dtype="<u8").reshape(-1)
+    if words.size < (n + 63) // 64:
+        raise ValueError(f"{words.size} bitmap words for {n} items")
+    if n == 0:
+        return np.empty(0, dtype=np.int64)
+    flags = np.unpackbits(words[:(n + 63) // 64].view(np.uint8), bitorder="little")[:n]
+    return np.flatnonzero(flags).astype(np.int64)
+
+
+def _expected_rows(expected, n: int) -> tuple[np.ndarray, np.ndarray]:
+    """The expected digests of a verify call as an (n, 32) uint8 array for the
+    device, plus the indices that are a mismatch already on the host: a
+    sequence entry whose length is not 32 (bytes.Equal of unequal lengths);
+    such an entry goes to the device as 32 zero bytes."""
+    if isinstance(expected, np.ndarray):
+        if expected.dtype != np.uint8 or expected.shape != (n, 32):
+            raise ValueError(f"expected must be a uint8 array of shape ({n}, 32)")
+        return np.ascontiguousarray(expected), np.empty(0, dtype=np.int64)
+    rows = list(expected)
+    if len(rows) != n:
+        raise ValueError(f"{len(rows)} expected digests for {n} items")
+    bad = [i for i, d in enumerate(rows) if len(d) != 32]
+    for i in bad:
+        rows[i] = bytes(32)
+    arr = np.frombuffer(b"".join(bytes(d) for d in rows), dtype=np.uint8).reshape(n, 32)
+    return arr, np.asarray(bad, dtype=np.int64)
 
 
 def dedup_plan(requests) -> tuple[np.ndarray, int]:
@@ -347,7 +380,62 @@ class Engine:
             )
         return out
 
+    # ------------------------------------------------- verify on the device
+    def _verdict(self, call, n: int, expected) -> np.ndarray:
+        """Runs one mirsha_verify_* call (``call(expected_ptr, bits_ptr, count_ref)``)
+        and returns the sorted mismatching indices, host-side length mismatches included."""
+        exp, short = _expected_rows(expected, n)
+        if n == 0:
+            return np.empty(0, dtype=np.int64)
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        count = ctypes.c_uint32(0)
+        self._check(call(_ptr(exp), _ptr(bits), ctypes.byref(count)))
+        bad = mismatch_indices(bits, n)
+        if bad.size != count.value:
+            raise MirshaError(_lib.MIRSHA_EHIP, f"verify: bitmap has {bad.size} bits set, count is {count.value}")
+        return np.union1d(bad, short) if short.size else bad
+
+    def verify_slices(self, requests, expected) -> np.ndarray:
+        """Hash each request (as hash_slices) and compare with expected[i] on the
+        device (VerifyRequest, state_machine.go:408-417): the sorted indices
+        whose digest differs.  ``expected``: (n, 32) uint8 array or a sequence
+        of bytes (an entry that is not 32 bytes long is a mismatch).  Only the
+        verdict (a bitmap and a count) comes back from the device."""
+        sl = requests if isinstance(requests, SliceArrays) else SliceArrays.from_requests(requests)
+        return self._verdict(lambda e, b, c: self._lib.mirsha_verify_slices(
+            self.ctx, sl.ptr_p, sl.len_p, sl.first_p, sl.n, e, b, c), sl.n, expected)
+
+    def verify_batch(self, arena, off: Sequence[int], length: Sequence[int], expected) -> np.ndarray:
+        """verify_slices over requests packed in one arena (hash_batch's arguments)."""
+        a = _as_u8(arena)
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        ln = np.ascontiguousarray(length, dtype=np.uint32)
+        if o.shape != ln.shape:
+            raise ValueError("off and len differ in length")
+        n = int(o.size)
+        return self._verdict(lambda e, b, c: self._lib.mirsha_verify_batch(
+            self.ctx, _ptr(a), a.size, _ptr(o), _ptr(ln), n, e, b, c), n, expected)
+
+    def verify_digest_lists(self, digests, idx, list_first, expected) -> np.ndarray:
+        """digest_lists with one expected digest per list, compared on the device
+        (VerifyBatch, batch_tracker.go:139-174): the sorted mismatching list indices."""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        ix = np.ascontiguousarray(idx, dtype=np.uint32)
+        fs = np.ascontiguousarray(list_first, dtype=np.uint32)
+        nl = int(fs.size) - 1
+        if nl < 0:
+            raise ValueError("list_first needs n_lists + 1 entries")
+        return self._verdict(lambda e, b, c: self._lib.mirsha_verify_digest_lists(
+            self.ctx, _ptr(d), d.shape[0], _ptr(ix), _ptr(fs), nl, e, b, c), nl, expected)
+
     # ---------------------------------------------------------- device API
+    def verify_digests_device(self, d_digests: int, d_expected: int, n: int, d_bits: int, d_count: int) -> None:
+        """Compare n device digests with n expected ones (mirsha_verify_digests_device):
+        mismatch bitmap (ceil(n/64) uint64 words) to d_bits, count (uint32) to
+        d_count; asynchronous on the engine's stream."""
+        self._check(self._lib.mirsha_verify_digests_device(self.ctx, d_digests or None, d_expected or None, int(n),
+                                                           d_bits or None, d_count or None))
+
     def hash_batch_device(self, d_arena: int, arena_len: int, d_off: int, d_len: int, d_order: int | None,
                           n: int, d_out: int) -> None:
         self._check(self._lib.mirsha_hash_batch_device(self.ctx, d_arena, arena_len, d_off, d_len, d_order, n, d_out))
@@ -689,6 +777,8 @@ __all__ = [
     "KERNEL_CHAIN",
     "KERNEL_FUSED",
     "KERNEL_OVERLAP",
+    "KERNEL_VERIFY",
+    "mismatch_indices",
     "PIPELINE_SEQUENTIAL",
     "PIPELINE_FUSED",
     "PIPELINE_AUTO",

@@ -287,6 +287,74 @@ def hash_results(event: bytes) -> List[LoggedHashResult]:
     return out
 
 
+def _ack_digests(body: bytes, field: int) -> List[bytes]:
+    """RequestAck.digest (field 3) of every ack in repeated field `field`, in
+    wire order; a null request's empty digest stays an empty slice."""
+    return [_get(parse_fields(ack), 3, b"") for n, _, ack in parse_fields(body) if n == field]
+
+
+def _set_entries(fields, num: int) -> List[Tuple[int, int, bytes]]:
+    out = []
+    for n, _, v in fields:
+        if n == num:
+            f = parse_fields(v)
+            out.append((_get(f, 1, 0), _get(f, 2, 0), _get(f, 3, b"")))
+    return out
+
+
+def origin_hash_data(hash_result: bytes) -> Tuple[int, bytes, Optional[List[bytes]]]:
+    """(kind, recorded digest, data) of one encoded HashResult
+    (mirbft.proto:408-448): the ``[][]byte`` its origin had hashed, rebuilt
+    from the Origin the log keeps, for all five kinds.  Absent proto3 fields
+    read as 0 / empty.  ``data`` is None when nothing can be rebuilt: a
+    Request / VerifyRequest whose payload was redacted, or no origin at all.
+
+    Request / VerifyRequest   hashdata.request_hash_data (as hash_results)
+    Batch (request_acks = 5), VerifyBatch (request_acks = 3)
+                              one slice per ack digest, wire order, empty
+                              digests kept (sequence.go:154-157,
+                              batch_tracker.go:147-150, client_tracker.go:840-847)
+    EpochChange (field 3)     epochChangeHashData, stateless.go:311-340:
+                              new_epoch, checkpoints, P-set, Q-set"""
+    hf = parse_fields(hash_result)
+    digest = _get(hf, 1, b"")
+    hw, hv = _oneof(hf, _HR_TYPES)
+    data = None
+    if hw == HR_REQUEST:
+        req = parse_fields(_get(parse_fields(hv), 2, b""))
+        payload = _get(req, 3, b"")
+        if payload:
+            data = hashdata.request_hash_data(_get(req, 1, 0), _get(req, 2, 0), payload)
+    elif hw == HR_VERIFY_REQUEST:
+        vf = parse_fields(hv)
+        payload = _get(vf, 3, b"")
+        if payload:
+            ack = parse_fields(_get(vf, 2, b""))
+            data = hashdata.request_hash_data(_get(ack, 1, 0), _get(ack, 2, 0), payload)
+    elif hw == HR_BATCH:
+        data = hashdata.batch_hash_data(_ack_digests(hv, 5))
+    elif hw == HR_VERIFY_BATCH:
+        data = hashdata.batch_hash_data(_ack_digests(hv, 3))
+    elif hw == HR_EPOCH_CHANGE:
+        ec = parse_fields(_get(parse_fields(hv), 3, b""))
+        cps = []
+        for n, _, v in ec:
+            if n == 2:
+                f = parse_fields(v)
+                cps.append((_get(f, 1, 0), _get(f, 2, b"")))
+        data = hashdata.epoch_change_hash_data(_get(ec, 1, 0), cps, _set_entries(ec, 3), _set_entries(ec, 4))
+    return hw or 0, digest, data
+
+
+def add_results_digests(event: bytes) -> List[bytes]:
+    """The encoded HashResults of an AddResults StateEvent, in order (empty for
+    other events): the inputs of :func:`origin_hash_data`."""
+    which, val = _oneof(parse_fields(event), _SE_TYPES)
+    if which != SE_ADD_RESULTS:
+        return []
+    return [hr for n, _, hr in parse_fields(val) if n == 1]
+
+
 def rehash_log(events: Sequence[RecordedEvent], engine) -> Tuple[int, List[int]]:
     """Re-hash every payload-carrying Request / VerifyRequest result of a log in
     ONE engine call (``Engine.hash_slices``) and compare with the recorded

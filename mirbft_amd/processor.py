@@ -22,6 +22,17 @@ epoch_target.go:459-477).  ``Processor.submit`` / ``PendingResults.wait`` is
 the asynchronous form (mirsha_submit_slices / mirsha_wait): the cycle's
 requests are packed before ``submit`` returns and the digests are collected,
 in origin order, after the caller's other work for the cycle.
+
+``verify_on_device=True``: a HashRequest that carries the digest its origin
+expects (``expected``: RequestAck.Digest of a VerifyRequest,
+state_machine.go:408-417; ExpectedDigest of a VerifyBatch,
+batch_tracker.go:139-174) is hashed AND compared on the device
+(``Engine.verify_slices``), and only a verdict comes back: a match yields
+``digest = expected``, the few mismatches are hashed again with
+``hash_slices`` so the caller still sees the true digest.  ``process()``
+returns the same ActionResults with the flag on or off.  ``submit()`` is
+unchanged by the flag: the asynchronous ring has no verify form and always
+hashes.
 """
 from __future__ import annotations
 
@@ -36,6 +47,9 @@ from .engine import Engine
 class HashRequest:
     data: list  # [][]byte; concatenation is hashed
     origin: Any = None  # opaque to the hasher (actions.go:152-156)
+    # The digest the origin expects (VerifyRequest / VerifyBatch), if it carries
+    # one: read only by a Processor with verify_on_device=True.
+    expected: Optional[bytes] = None
 
 
 @dataclass(eq=False)
@@ -110,18 +124,43 @@ class PendingResults:
 class Processor:
     """Hash stage of mirbft.Processor; batches one Ready() cycle per device call."""
 
-    def __init__(self, engine: Optional[Engine] = None, device: int = 0, dedup: bool = False):
+    def __init__(self, engine: Optional[Engine] = None, device: int = 0, dedup: bool = False,
+                 verify_on_device: bool = False):
         self.engine = engine if engine is not None else Engine(device)
         self.dedup = dedup
+        self.verify_on_device = verify_on_device
 
     def process(self, actions: Actions) -> ActionResults:
         reqs = actions.hash
         if not reqs:
             return ActionResults(digests=[])
+        if self.verify_on_device:
+            return self._process_verifying(reqs)
         return _results(reqs, self.engine.hash_slices([r.data for r in reqs], dedup=self.dedup))
 
+    def _process_verifying(self, reqs) -> ActionResults:
+        """One cycle split in two device calls: requests with ``expected`` are
+        hashed and compared on the device, the rest hashed as usual.  Same
+        ActionResults as the plain path (digests, order, back-pointers)."""
+        check = [i for i, r in enumerate(reqs) if r.expected is not None]
+        plain = [i for i, r in enumerate(reqs) if r.expected is None]
+        digests: list = [None] * len(reqs)
+        if check:
+            bad = self.engine.verify_slices([reqs[i].data for i in check], [reqs[i].expected for i in check])
+            wrong = [check[int(k)] for k in bad]
+            for i in check:
+                digests[i] = bytes(reqs[i].expected)
+            plain = sorted(plain + wrong)  # mismatches: the true digest, with the rest of the cycle
+        if plain:
+            got = self.engine.hash_slices([reqs[i].data for i in plain], dedup=self.dedup)
+            for k, i in enumerate(plain):
+                digests[i] = got[k].tobytes()
+        return ActionResults(digests=[HashResult(digest=digests[i], request=r) for i, r in enumerate(reqs)])
+
     def submit(self, actions: Actions) -> PendingResults:
-        """Asynchronous process(): queue the cycle's hashing, return at once."""
+        """Asynchronous process(): queue the cycle's hashing, return at once.
+        Always hashes (``verify_on_device`` does not apply: the ring has no
+        verify form)."""
         reqs = list(actions.hash)
         ticket = self.engine.submit_slices([r.data for r in reqs], dedup=self.dedup) if reqs else None
         return PendingResults(self.engine, reqs, ticket)
@@ -135,8 +174,8 @@ class ProcessorWorkPool(Processor):
     """
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, hash_workers: int = 0,
-                 transmit_workers: int = 0, dedup: bool = False):
-        super().__init__(engine, device, dedup)
+                 transmit_workers: int = 0, dedup: bool = False, verify_on_device: bool = False):
+        super().__init__(engine, device, dedup, verify_on_device)
         self._mutex = threading.Lock()
         self.hash_workers = hash_workers
 
@@ -144,8 +183,14 @@ class ProcessorWorkPool(Processor):
         """processor.go:447-470: the pool hashes while the WAL and the sends
         proceed.  Here the cycle's hashing is submitted first, ``overlap()``
         (the caller's persist / transmit work) runs while the GPU hashes, then
-        the digests are collected in origin order."""
+        the digests are collected in origin order.  With ``verify_on_device``
+        the cycle goes through the synchronous split of ``Processor.process``
+        (``overlap()`` runs first: the verify calls are synchronous)."""
         with self._mutex:  # processor.go:448-449
+            if self.verify_on_device:
+                if overlap is not None:
+                    overlap()
+                return Processor.process(self, actions)
             pending = self.submit(actions)
             if overlap is not None:
                 overlap()
