@@ -100,7 +100,8 @@ int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
  * kernel: 0 = message kernel, 1 = digest-list (batch) kernel, 2 = generator
  * and clock probe, 3 = batch-chain kernel, 4 = fused request -> batch kernel
  * (one persistent launch per run), 5 = overlapped-cycles kernel
- * (mirsha_pipeline_overlap_device), 6 = digest compare kernel (mirsha_verify_*).
+ * (mirsha_pipeline_overlap_device), 6 = digest compare kernel (mirsha_verify_*),
+ * 7 = select kernel of the mixed ring submissions (mirsha_submit_*_expect).
  * set_timing_mask: bit k on = kernel k is timed while timing is enabled
  * (default: all). */
 int mirsha_ctx_set_timing(mirsha_ctx* ctx, int enable);
@@ -201,6 +202,65 @@ int mirsha_poll(mirsha_ctx* ctx, uint64_t ticket, int* done);
 int mirsha_submit_batch(mirsha_ctx* ctx, const uint8_t* arena, uint64_t arena_len,
                         const uint64_t* off, const uint32_t* len, uint32_t n,
                         uint8_t* digests_out, uint64_t* ticket_out);
+
+/* Mixed hash-and-verify cycles.  A real cycle's actions.Hash mixes all five
+ * origin kinds and only VerifyRequest (state_machine.go:408-417) and
+ * VerifyBatch (batch_tracker.go:139-174) carry an expected digest: these are
+ * mirsha_submit_slices / mirsha_submit_batch (same argument rules, error
+ * codes, messages, arena routes, ring, tickets, mirsha_wait / mirsha_poll)
+ * where each request may or may not carry an expectation.  The comparison
+ * runs on the device behind the hashing kernel; the caller gets a verdict, and
+ * digests only where it does not already hold them.
+ *   expect_of       the m indices of the requests that carry an expectation:
+ *                   strictly increasing, each < n (else MIRSHA_EINVAL);
+ *   expected        32 m bytes, row k = the expectation of request
+ *                   expect_of[k].  Both are read before the call returns and
+ *                   travel H2D with the metadata;
+ *   flags           must be 0 (MIRSHA_SUBMIT_DEDUP is MIRSHA_EINVAL: dedup and
+ *                   expectations do not combine in one submission).
+ * When the ticket retires (mirsha_wait, a mirsha_poll that reports done, or a
+ * later submission reusing its ring slot):
+ *   bits_out        (may be NULL) ceil(n / 64) words, bit i & 63 of word
+ *                   i >> 6 set exactly when request i carries an expectation
+ *                   and its digest differs from it in any bit; bits at or
+ *                   beyond n are 0;
+ *   *n_mismatch_out (required) the number of set bits;
+ *   digests_out     row i holds request i's digest for every request WITHOUT
+ *                   an expectation and for every MISMATCH.  The 32 bytes of a
+ *                   matching request are not written (they keep the caller's
+ *                   bytes): the caller holds that digest already, it equals
+ *                   its expectation.
+ * digests_out, bits_out and n_mismatch_out must stay valid until then.  A
+ * page-locked, 16-byte aligned digests_out receives the kept rows from the
+ * select kernel itself; otherwise the kernel stores them into the context's
+ * page-locked rows and exactly the kept rows are copied out at retirement.
+ * Either way a matching request's digest never crosses PCIe.  A validation
+ * failure queues nothing and consumes no ticket.  n == 0: a valid ticket,
+ * count 0.  m == 0: the plain submission, with an all-zero bitmap.
+ * mirsha_ctx_host_profile: scatter = the copy of the kept rows plus the
+ * verdict.  mirsha_hash_slices_expect = submit + wait. */
+int mirsha_submit_slices_expect(mirsha_ctx* ctx, const uint8_t* const* slice_ptr,
+                                const uint64_t* slice_len, const uint32_t* slice_first, uint32_t n,
+                                const uint32_t* expect_of, const uint8_t* expected, uint32_t m,
+                                uint8_t* digests_out, uint64_t* bits_out, uint32_t* n_mismatch_out,
+                                int flags, uint64_t* ticket_out);
+int mirsha_submit_batch_expect(mirsha_ctx* ctx, const uint8_t* arena, uint64_t arena_len,
+                               const uint64_t* off, const uint32_t* len, uint32_t n,
+                               const uint32_t* expect_of, const uint8_t* expected, uint32_t m,
+                               uint8_t* digests_out, uint64_t* bits_out, uint32_t* n_mismatch_out,
+                               uint64_t* ticket_out);
+int mirsha_hash_slices_expect(mirsha_ctx* ctx, const uint8_t* const* slice_ptr,
+                              const uint64_t* slice_len, const uint32_t* slice_first, uint32_t n,
+                              const uint32_t* expect_of, const uint8_t* expected, uint32_t m,
+                              uint8_t* digests_out, uint64_t* bits_out, uint32_t* n_mismatch_out);
+/* Host-only (no device, no context), like mirsha_dedup_plan: the plan the
+ * calls above send to the device.  has_out: ceil(n / 64) words, bit i & 63 of
+ * word i >> 6 set exactly when request i is listed in expect_of; base_out[w] =
+ * set bits in words 0..w-1, so request i's row of `expected` is
+ * base[i >> 6] + popcount(has[i >> 6] & ((1 << (i & 63)) - 1)).  expect_of not
+ * strictly increasing, an index >= n or m > n: MIRSHA_EINVAL. */
+int mirsha_expect_plan(const uint32_t* expect_of, uint32_t m, uint32_t n, uint64_t* has_out,
+                       uint32_t* base_out);
 
 /* Host-side phases (milliseconds) of the context's last host-API call.
  * Slice submissions (mirsha_submit_slices / mirsha_hash_slices_dedup):

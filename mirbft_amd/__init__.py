@@ -7,8 +7,8 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 """
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
-from .engine import (CheckpointChains, Engine, MultiEngine, SliceArrays, Ticket, bucket_order, dedup_plan, device_count,
-                     hash_batch_multi, mismatch_indices)
+from .engine import (CheckpointChains, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order, dedup_plan,
+                     device_count, expect_bitmap, expect_plan, hash_batch_multi, mismatch_indices)
 from .processor import (ActionResults, Actions, GpuHash, HashRequest, HashResult, PendingResults, Processor,
                         ProcessorWorkPool, gpu_hasher)
 
@@ -17,7 +17,10 @@ __all__ = [
     "CheckpointChains",
     "SliceArrays",
     "Ticket",
+    "ExpectTicket",
     "dedup_plan",
+    "expect_plan",
+    "expect_bitmap",
     "PendingResults",
     "MirshaError",
     "MirshaUnavailable",

@@ -61,6 +61,21 @@ SIGNATURES = {
     "mirsha_wait": (c_int, [c_void_p, c_uint64]),
     "mirsha_poll": (c_int, [c_void_p, c_uint64, POINTER(c_int)]),
     "mirsha_submit_batch": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, _u64p]),
+    "mirsha_submit_slices_expect": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+         c_int, _u64p],
+    ),
+    "mirsha_submit_batch_expect": (
+        c_int,
+        [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p,
+         c_void_p, _u64p],
+    ),
+    "mirsha_hash_slices_expect": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p],
+    ),
+    "mirsha_expect_plan": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
     "mirsha_hash_requests_then_batches": (
         c_int,
         [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p],

@@ -164,6 +164,7 @@ void mirsha_ctx_destroy(mirsha_ctx* c) {
     if (c->xout) (void)hipStreamDestroy(c->xout);
     for (auto& sl : c->slots) {
         sl.stage.release(); sl.dig.release(); sl.dev.release(); sl.stage2.release(); sl.dev2.release();
+        sl.xp.stage.release(); sl.xp.verdict.release(); sl.xp.dev.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
         if (sl.ev_kern) (void)hipEventDestroy(sl.ev_kern);

@@ -6,19 +6,166 @@
 
 namespace mirsha_api {
 
+// ---- mixed hash-and-verify cycles (mirsha_submit_*_expect) -------------------
+// What a mixed submission adds to the plain one's arguments.
+struct ExpectArgs {
+    const uint32_t* expect_of;
+    const uint8_t* expected;
+    uint32_t m;
+    uint64_t* bits_out;
+    uint32_t* n_mismatch_out;
+};
+
+// The argument checks of a mixed submission, and its plan (mirsha_expect_plan)
+// into the context's scratch.  Nothing is queued and no ticket is consumed.
+static int expect_validate(mirsha_ctx* c, const ExpectArgs& xa, uint32_t n, int flags) {
+    if (flags & MIRSHA_SUBMIT_DEDUP)
+        return fail(c, MIRSHA_EINVAL, "MIRSHA_SUBMIT_DEDUP does not combine with expectations");
+    if (flags) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
+    if (!xa.n_mismatch_out) return fail(c, MIRSHA_EINVAL, "n_mismatch_out is NULL");
+    if (xa.m && (!xa.expect_of || !xa.expected)) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (xa.m > n) return fail(c, MIRSHA_EINVAL, "%u expectations for %u requests", xa.m, n);
+    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) >> 6);
+    if (c->xp_has.size() < words) c->xp_has.resize(words);
+    if (c->xp_base.size() < words) c->xp_base.resize(words);
+    if (mirsha_expect_plan(xa.expect_of, xa.m, n, c->xp_has.data(), c->xp_base.data()) != MIRSHA_OK)
+        return fail(c, MIRSHA_EINVAL, "expect_of must be strictly increasing with every index below %u", n);
+    return MIRSHA_OK;
+}
+
+// Page-locked, 16-byte aligned caller rows a kernel on the context's device may
+// store into: their device address, else NULL.
+static uint8_t* kernel_rows(mirsha_ctx* c, uint8_t* out) {
+    if (!out || (reinterpret_cast<uintptr_t>(out) & 15u) || !kernel_writable_host(out, c->device)) return nullptr;
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, out, 0) == hipSuccess) return static_cast<uint8_t*>(dp);
+    (void)hipGetLastError();
+    return nullptr;
+}
+
+// Sizes the (free) slot's expectation staging, device block and verdict, and
+// stages the plan.
+static int expect_stage(mirsha_ctx* c, AsyncSlot& sl, const ExpectArgs& xa, uint32_t n) {
+    ExpectSlot& x = sl.xp;
+    x.words = (uint32_t)(((uint64_t)n + 63u) >> 6);
+    x.o_exp = align16(12ull * x.words);
+    x.h2d = x.o_exp + 32ull * xa.m;
+    x.o_ver = align16(x.h2d);
+    HIP_TRY(c, x.stage.ensure(std::max<uint64_t>(x.h2d, 16)));
+    HIP_TRY(c, x.verdict.ensure(8 + 8ull * x.words));
+    HIP_TRY(c, x.dev.ensure(x.o_ver + 8 + 8ull * x.words));
+    uint8_t* st = x.stage.as<uint8_t>();
+    memcpy(st, c->xp_has.data(), 8ull * x.words);
+    memcpy(st + 8ull * x.words, c->xp_base.data(), 4ull * x.words);
+    return MIRSHA_OK;
+}
+
+// Copies the expected rows into the slot's staging (before the call returns:
+// the caller may reuse them at once) and queues the expectation block's H2D.
+// Called once the request bytes' DMA is queued, so the copy runs under it.
+static int expect_h2d(mirsha_ctx* c, AsyncSlot& sl, const ExpectArgs& xa, hipStream_t s) {
+    ExpectSlot& x = sl.xp;
+    const uint64_t bytes = 32ull * xa.m;
+    mirsha::host::pack_range(xa.expected, nullptr, nullptr, nullptr, 0, nullptr, 0, bytes,
+                             x.stage.as<uint8_t>() + x.o_exp, mirsha::host::threads_for(bytes, 1u << 20), true);
+    HIP_TRY(c, hipMemcpyAsync(x.dev.p, x.stage.p, x.h2d, hipMemcpyHostToDevice, s));
+    return MIRSHA_OK;
+}
+
+// Behind the hashing kernel on c->stream: the count's reset,
+// expect_select_kernel (timing id 7) over the n device digests, the kept rows
+// stored to `rows` (host-visible, device address), and the verdict's copy.
+static int expect_queue(mirsha_ctx* c, AsyncSlot& sl, const uint8_t* d_digests, uint32_t n, uint8_t* rows) {
+    ExpectSlot& x = sl.xp;
+    uint8_t* xd = x.dev.as<uint8_t>();
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(xd + x.o_ver);
+    uint64_t* d_bits = reinterpret_cast<uint64_t*>(xd + x.o_ver + 8);
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(uint32_t), c->stream));
+    if (int rc = timed_launch(c, kTimerExpect, [&] {
+            return mirsha::launch_expect_select(d_digests, xd + x.o_exp, reinterpret_cast<const uint64_t*>(xd),
+                                                reinterpret_cast<const uint32_t*>(xd + 8ull * x.words), n, rows,
+                                                d_bits, d_count, c->stream);
+        }))
+        return rc;
+    HIP_TRY(c, hipMemcpyAsync(x.verdict.p, xd + x.o_ver, 8 + 8ull * x.words, hipMemcpyDeviceToHost, c->stream));
+    return MIRSHA_OK;
+}
+
+// The slot's page-locked digest rows, as the select kernel addresses them.
+static int slot_rows(mirsha_ctx* c, AsyncSlot& sl, uint8_t** rows) {
+    void* dp = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer(&dp, sl.dig.p, 0));
+    *rows = static_cast<uint8_t*>(dp);
+    return MIRSHA_OK;
+}
+
+// A retired mixed submission: the kept rows (requests without an expectation,
+// and mismatches) from the slot's rows to the caller unless the kernel stored
+// them there itself, walking ~has | mis run by run; then the verdict.
+static void expect_complete(AsyncSlot& sl) {
+    ExpectSlot& x = sl.xp;
+    const uint32_t n = sl.n;
+    if (!x.select) {  // no expectation: every row is already the caller's, nothing differs
+        if (x.user_bits) memset(x.user_bits, 0, 8ull * x.words);
+        *x.user_count = 0;
+        return;
+    }
+    const uint64_t* has = x.stage.as<uint64_t>();
+    const uint8_t* v = x.verdict.as<uint8_t>();
+    const uint64_t* mis = reinterpret_cast<const uint64_t*>(v + 8);
+    if (!x.rows_direct) {
+        const uint8_t* d = sl.dig.as<uint8_t>();
+        uint64_t run0 = 0, run = 0;
+        auto flush = [&] {
+            if (run) memcpy(sl.user_out + 32ull * run0, d + 32ull * run0, 32ull * run);
+            run = 0;
+        };
+        for (uint32_t w = 0; w < x.words; w++) {
+            uint64_t keep = ~has[w] | mis[w];
+            if (w == x.words - 1 && (n & 63u)) keep &= (1ull << (n & 63u)) - 1ull;
+            uint32_t pos = 0;
+            while (pos < 64) {
+                const uint64_t rest = keep >> pos;
+                if (!rest) {
+                    flush();
+                    break;
+                }
+                const uint32_t z = (uint32_t)__builtin_ctzll(rest);
+                if (z) {
+                    flush();
+                    pos += z;
+                    continue;
+                }
+                const uint64_t inv = ~rest;
+                const uint32_t ones = inv ? (uint32_t)__builtin_ctzll(inv) : 64u;
+                if (!run) run0 = 64ull * w + pos;
+                run += ones;
+                pos += ones;
+                if (pos < 64) flush();  // the run ends inside this word
+            }
+        }
+        flush();
+    }
+    if (x.user_bits) memcpy(x.user_bits, mis, 8ull * x.words);
+    memcpy(x.user_count, v, sizeof(uint32_t));
+}
+
 // Copies a completed submission's digests to the caller, in origin order.
 int async_complete(mirsha_ctx* c, AsyncSlot& sl) {
     HIP_TRY(c, hipEventSynchronize(sl.done));
     const auto t_done = Clock::now();
     sl.prof[MIRSHA_PROF_DEVICE] = std::chrono::duration<double, std::milli>(t_done - sl.t_queued).count();
     const uint8_t* d = sl.dig.as<uint8_t>();
-    if (sl.direct) {
+    if (sl.xp.on && sl.xp.select) {
+        // mixed submission: only the kept rows are copied (expect_complete)
+    } else if (sl.direct) {
         // mirsha_submit_batch into page-locked digests_out: already there
     } else if (sl.rank.empty()) {
         if (sl.n) memcpy(sl.user_out, d, 32ull * sl.n);
     } else {
         for (uint32_t i = 0; i < sl.n; i++) memcpy(sl.user_out + 32ull * i, d + 32ull * sl.rank[i], 32);
     }
+    if (sl.xp.on) expect_complete(sl);
     sl.busy = false;
     c->done_ticket = std::max(c->done_ticket, sl.ticket);
     sl.prof[MIRSHA_PROF_SCATTER] = ms_since(t_done);
@@ -40,7 +187,9 @@ int async_wait_upto(mirsha_ctx* c, uint64_t ticket) {
 
 int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
                  const uint32_t* slice_first, uint32_t n, uint8_t* out, int flags, uint64_t* ticket_out,
-                 uint32_t* n_unique_out) {
+                 uint32_t* n_unique_out, const ExpectArgs* xa = nullptr) {
+    if (xa)
+        if (int rc = expect_validate(c, *xa, n, flags)) return rc;
     if (flags & ~MIRSHA_SUBMIT_DEDUP) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
     auto t0 = Clock::now();
     // Which requests reach the GPU: all, or one per distinct content.  With
@@ -69,8 +218,21 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
         if (int rc = async_wait_upto(c, sl.ticket)) return rc;  // ring full: retire the oldest
     sl.rank.clear();
     sl.direct = false;
+    sl.xp.on = sl.xp.select = false;
     HIP_TRY(c, sl.dig.ensure(32ull * std::max<uint32_t>(n, 1)));
     if (!sl.done) HIP_TRY(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    // Mixed submission with expectations: the select kernel stands where the
+    // digests' D2H copy stood, storing the kept rows into a page-locked
+    // digests_out or else into the slot's page-locked rows.
+    const bool sel = xa && xa->m;
+    uint8_t* sel_rows = nullptr;
+    if (sel) {
+        if (int rc = expect_stage(c, sl, *xa, n)) return rc;
+        sel_rows = kernel_rows(c, out);
+        sl.xp.rows_direct = sel_rows != nullptr;
+        if (!sel_rows)
+            if (int rc = slot_rows(c, sl, &sel_rows)) return rc;
+    }
     ph[MIRSHA_PROF_PLAN] = ms_since(t0);
     // Packs requests `ids` (identity when null) into `stage`, and queues their
     // digests into rows [row0, row0 + m) of sl.dig.
@@ -82,7 +244,8 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
             return fail(c, MIRSHA_ERANGE, "submission of %llu bytes exceeds one device arena (%u); split it",
                         (unsigned long long)bytes, MIRSHA_MAX_DEVICE_ARENA_BYTES);
         const uint64_t o_off = align8(bytes + kArenaSlack);
-        const uint64_t o_len = o_off + 8ull * m, o_ord = o_len + 4ull * m, o_end = align8(o_ord + 4ull * m);
+        const uint64_t o_len = o_off + 8ull * m, o_ord = o_len + 4ull * m;
+        const uint64_t o_end = sel ? align16(o_ord + 4ull * m) : align8(o_ord + 4ull * m);  // select: 128-bit rows
         const uint64_t o_dig = o_end;
         HIP_TRY(c, stage.ensure(o_end));
         HIP_TRY(c, dev.ensure(o_dig + 32ull * std::max<uint32_t>(m, 1)));
@@ -103,6 +266,8 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
         uint8_t* dv = dev.as<uint8_t>();
         if (m) {
             HIP_TRY(c, hipMemcpyAsync(dv, st, o_end, hipMemcpyHostToDevice, c->stream));
+            if (sel)
+                if (int rc = expect_h2d(c, sl, *xa, c->stream)) return rc;
             int rc = timed_launch(c, 0, [&] {
                 return mirsha::launch_msgs(dv, bytes, reinterpret_cast<const uint64_t*>(dv + o_off),
                                            reinterpret_cast<const uint32_t*>(dv + o_len),
@@ -110,8 +275,12 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
                                            dv + o_dig, c->variant, c->stream);
             });
             if (rc) return rc;
-            HIP_TRY(c, hipMemcpyAsync(sl.dig.as<uint8_t>() + 32ull * row0, dv + o_dig, 32ull * m,
-                                      hipMemcpyDeviceToHost, c->stream));
+            if (sel) {
+                if (int rc2 = expect_queue(c, sl, dv + o_dig, m, sel_rows)) return rc2;
+            } else {
+                HIP_TRY(c, hipMemcpyAsync(sl.dig.as<uint8_t>() + 32ull * row0, dv + o_dig, 32ull * m,
+                                          hipMemcpyDeviceToHost, c->stream));
+            }
         }
         ph[MIRSHA_PROF_PACK] += ms_since(tq);
         return MIRSHA_OK;
@@ -174,6 +343,13 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     sl.user_out = out;
     sl.n = n;
     sl.m = m;
+    if (xa) {
+        sl.xp.on = true;
+        sl.xp.select = sel;
+        sl.xp.words = (uint32_t)(((uint64_t)n + 63u) >> 6);
+        sl.xp.user_bits = xa->bits_out;
+        sl.xp.user_count = xa->n_mismatch_out;
+    }
     sl.ticket = c->next_ticket++;
     for (int k = 0; k < MIRSHA_PROF_PHASES; k++) sl.prof[k] = ph[k];
     if (ticket_out) *ticket_out = sl.ticket;
@@ -192,9 +368,12 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
 // ticket retires.  The Go binding's chunked HashBatch packs
 // chunk k + 1 of a Ready() cycle while chunk k's DMA, kernel and D2H run.
 int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
-                       const uint32_t* len, uint32_t n, uint8_t* out, uint64_t* ticket_out) {
+                       const uint32_t* len, uint32_t n, uint8_t* out, uint64_t* ticket_out,
+                       const ExpectArgs* xa = nullptr) {
     auto t0 = Clock::now();
     const auto t_entry = t0;
+    if (xa)
+        if (int rc = expect_validate(c, *xa, n, 0)) return rc;
     double ph[MIRSHA_PROF_PHASES] = {};
     // MIRSHA_SUBMIT_TRACE=1 (with MIRSHA_AB=1): a submission slower than 2 ms
     // prints where its time went (ms since entry at each step) on stderr.
@@ -311,6 +490,7 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     tr[2] = ms_since(t_entry);
     t0 = Clock::now();
     sl.rank.clear();
+    sl.xp.on = sl.xp.select = false;
     for (hipEvent_t* e : {&sl.done, &sl.ev_in, &sl.ev_kern})
         if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     // Request bytes in on xin, the kernel on the context stream; digests
@@ -337,9 +517,21 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
         else
             (void)hipGetLastError();
     }
-    if (!sl.direct) HIP_TRY(c, sl.dig.ensure(32ull * std::max<uint32_t>(n, 1)));
+    // Mixed submission with expectations: the hashing kernel keeps its digests
+    // on the device, and the select kernel behind it stores the kept rows into
+    // a kernel-writable digests_out, else into the slot's page-locked rows.
+    const bool sel = xa && xa->m;
+    uint8_t* sel_rows = kout;
+    if (!sl.direct || (sel && !kout)) HIP_TRY(c, sl.dig.ensure(32ull * std::max<uint32_t>(n, 1)));
+    if (sel) {
+        if (int rc = expect_stage(c, sl, *xa, n)) return rc;
+        sl.xp.rows_direct = kout != nullptr;
+        if (!kout)
+            if (int rc = slot_rows(c, sl, &sel_rows)) return rc;
+    }
     // device: [request bytes + slack | len u32 | order u32 | off u64 | digests]
-    const uint64_t d_meta = align8(bytes + kArenaSlack), d_dig = d_meta + o_end;
+    const uint64_t d_meta = align8(bytes + kArenaSlack);
+    const uint64_t d_dig = sel ? align16(d_meta + o_end) : d_meta + o_end;  // select: 128-bit rows
     size_t scan_bytes = 0;
     if (gapless) {
         HIP_TRY(c, mirsha::launch_offsets_scan(nullptr, scan_bytes, nullptr, nullptr, n, c->stream));
@@ -379,10 +571,15 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
             if (!from_caller && bytes) HIP_TRY(c, hipMemcpyAsync(dv, st, bytes, hipMemcpyHostToDevice, c->xin));
             // The metadata: behind the request bytes on xin when the kernel
             // stores the digests (one copy stream), else on the kernel stream.
+            // (the expectations of a mixed submission travel with it)
             if (kout) HIP_TRY(c, hipMemcpyAsync(dv + d_meta, mb, meta_copy, hipMemcpyHostToDevice, c->xin));
+            if (kout && sel)
+                if (int rc = expect_h2d(c, sl, *xa, c->xin)) return rc;
             HIP_TRY(c, hipEventRecord(sl.ev_in, c->xin));
             tq[0] = ms_since(t_entry);
             if (!kout) HIP_TRY(c, hipMemcpyAsync(dv + d_meta, mb, meta_copy, hipMemcpyHostToDevice, c->stream));
+            if (!kout && sel)
+                if (int rc = expect_h2d(c, sl, *xa, c->stream)) return rc;
             tq[1] = ms_since(t_entry);
             HIP_TRY(c, hipStreamWaitEvent(c->stream, sl.ev_in, 0));
             tq[2] = ms_since(t_entry);
@@ -395,10 +592,16 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
                     return mirsha::launch_msgs(dv, bytes, d_off, d_len,
                                                identity ? nullptr
                                                         : reinterpret_cast<const uint32_t*>(dv + d_meta + o_ord),
-                                               n, kout ? kout : dv + d_dig, c->variant, c->stream);
+                                               n, kout && !sel ? kout : dv + d_dig, c->variant, c->stream);
                 }))
                 return rc;
             tq[4] = ms_since(t_entry);
+            if (sel) {  // kept rows and verdict are in host memory when the verdict's copy ends
+                if (int rc = expect_queue(c, sl, dv + d_dig, n, sel_rows)) return rc;
+                HIP_TRY(c, hipEventRecord(sl.done, c->stream));
+                tq[7] = ms_since(t_entry);
+                return MIRSHA_OK;
+            }
             if (kout) {  // the digests are in host memory when the kernel ends
                 HIP_TRY(c, hipEventRecord(sl.done, c->stream));
                 tq[7] = ms_since(t_entry);
@@ -427,6 +630,13 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     sl.user_out = out;
     sl.n = n;
     sl.m = n;
+    if (xa) {
+        sl.xp.on = true;
+        sl.xp.select = sel;
+        sl.xp.words = (uint32_t)(((uint64_t)n + 63u) >> 6);
+        sl.xp.user_bits = xa->bits_out;
+        sl.xp.user_count = xa->n_mismatch_out;
+    }
     sl.ticket = c->next_ticket++;
     for (int k = 0; k < MIRSHA_PROF_PHASES; k++) sl.prof[k] = ph[k];
     *ticket_out = sl.ticket;
@@ -459,6 +669,36 @@ int mirsha_submit_batch(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len,
     if (!c || !ticket_out) return MIRSHA_EINVAL;
     if (n && (!off || !len || !digests_out || (!arena && arena_len))) return fail(c, MIRSHA_EINVAL, "NULL argument");
     return async_submit_arena(c, arena, arena_len, off, len, n, digests_out, ticket_out);
+}
+
+int mirsha_submit_slices_expect(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                                const uint32_t* slice_first, uint32_t n, const uint32_t* expect_of,
+                                const uint8_t* expected, uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
+                                uint32_t* n_mismatch_out, int flags, uint64_t* ticket_out) {
+    if (!c || !ticket_out) return MIRSHA_EINVAL;
+    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
+    return async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, flags, ticket_out, nullptr, &xa);
+}
+
+int mirsha_submit_batch_expect(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
+                               const uint32_t* len, uint32_t n, const uint32_t* expect_of, const uint8_t* expected,
+                               uint32_t m, uint8_t* digests_out, uint64_t* bits_out, uint32_t* n_mismatch_out,
+                               uint64_t* ticket_out) {
+    if (!c || !ticket_out) return MIRSHA_EINVAL;
+    if (n && (!off || !len || !digests_out || (!arena && arena_len))) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
+    return async_submit_arena(c, arena, arena_len, off, len, n, digests_out, ticket_out, &xa);
+}
+
+int mirsha_hash_slices_expect(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                              const uint32_t* slice_first, uint32_t n, const uint32_t* expect_of,
+                              const uint8_t* expected, uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
+                              uint32_t* n_mismatch_out) {
+    if (!c) return MIRSHA_EINVAL;
+    uint64_t t = 0;
+    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
+    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, 0, &t, nullptr, &xa)) return rc;
+    return async_wait_upto(c, t);
 }
 
 int mirsha_wait(mirsha_ctx* c, uint64_t ticket) {

@@ -11,7 +11,8 @@
 //   mirsha_plan.hip     request -> batch plans: sequential, fused (placement
 //                       probe), overlapped cycles (mirsha_pipeline_*)
 //   mirsha_async.hip    the asynchronous ring (mirsha_submit_* / wait / poll,
-//                       dedup)
+//                       dedup, mixed hash-and-verify cycles: *_expect)
+//   mirsha_expect.hip   the select kernel of the mixed submissions
 //   mirsha_multi.hip    the multi-device drop-in (mirsha_multi_*)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
@@ -38,6 +39,19 @@
 #include "mirsha_host.h"
 #include "mirsha_kernels.h"
 #include "sha256_device.h"
+
+namespace mirsha {
+// mirsha_expect.hip.  Mixed cycles (mirsha_submit_*_expect): compares the
+// digests of the requests marked in has[] (ceil(n / 64) words, base[] = set
+// bits before each word: mirsha_expect_plan) with their rows of `expected`,
+// stores the digest rows of every request without an expectation and of every
+// mismatch to row i of `out` (all arrays 16-byte aligned), writes every word
+// of the mismatch bitmap; *count += mismatches (the caller resets it on the
+// stream first).
+hipError_t launch_expect_select(const uint8_t* digests, const uint8_t* expected, const uint64_t* has,
+                                const uint32_t* base, uint32_t n, uint8_t* out, uint64_t* bits, uint32_t* count,
+                                hipStream_t s);
+}  // namespace mirsha
 
 namespace mirsha_api {
 
@@ -113,6 +127,20 @@ inline double ms_since(Clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
 }
 
+// The expectation side of a mixed submission (mirsha_submit_*_expect).
+struct ExpectSlot {
+    bool on = false;      // the ticket owes a verdict (bits_out / n_mismatch_out)
+    bool select = false;  // expect_select_kernel ran (m > 0): only the kept rows are the caller's
+    bool rows_direct = false;  // the kernel stored the kept rows into digests_out itself
+    uint32_t words = 0;   // ceil(n / 64)
+    uint64_t o_exp = 0, o_ver = 0, h2d = 0;  // offsets of the expected rows and the verdict; bytes of `stage`
+    uint64_t* user_bits = nullptr;
+    uint32_t* user_count = nullptr;
+    PinnedBuf stage;    // [has u64[words] | base u32[words], padded to 16 | expected 32 m]: H2D source
+    PinnedBuf verdict;  // [count u32, pad | mismatch bitmap u64[words]]: D2H target
+    DevBuf dev;         // stage's layout, then the verdict's (16-byte aligned)
+};
+
 struct AsyncSlot {
     PinnedBuf stage;  // [arena bytes | off u64[m] | len u32[m] | order u32[m]]
     Clock::time_point t_queued;  // when its device work was queued
@@ -129,10 +157,12 @@ struct AsyncSlot {
     uint32_t n = 0, m = 0;
     std::vector<uint32_t> rank;  // request -> row of `dig` (empty: identity)
     double prof[MIRSHA_PROF_PHASES] = {};  // this submission's host phases (published when it completes)
+    ExpectSlot xp;
 };
 
-constexpr int kKernelTimers = 7;  // timing ids 0-6 (mirsha.h, mirsha_ctx_kernel_time)
+constexpr int kKernelTimers = 8;  // timing ids 0-7 (mirsha.h, mirsha_ctx_kernel_time)
 constexpr int kTimerVerify = 6;
+constexpr int kTimerExpect = 7;
 
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -172,13 +202,15 @@ struct mirsha_ctx {
     // and zeroing per 2^20 requests.
     std::vector<uint32_t> sl_len;
     std::vector<uint64_t> sl_poff;
-    KernelTimer timers[kKernelTimers];  // msgs, lists, gen, chain, fused, overlap, verify
+    KernelTimer timers[kKernelTimers];  // msgs, lists, gen, chain, fused, overlap, verify, expect
     // Verify calls (mirsha_verify_*): the expected digests (pinned staging of a
     // pageable caller array, device copy) and the verdict block
     // [count u32, pad | bitmap u64[ceil(n/64)]] on the device and pinned.
     PinnedBuf h_expect, h_verdict;
     DevBuf d_expect, d_verdict;
     AsyncSlot slots[kAsyncSlots];
+    std::vector<uint64_t> xp_has;   // mirsha_expect_plan of the submission being validated
+    std::vector<uint32_t> xp_base;
     uint64_t next_ticket = 1;  // ticket of the next submission
     uint64_t done_ticket = 0;  // every ticket <= this one has completed
     double prof[MIRSHA_PROF_PHASES] = {};  // host phases of the last slice submission (ms)
@@ -316,6 +348,7 @@ inline bool kernel_writable_host(const void* p, int device) {
 }
 
 constexpr uint64_t align8(uint64_t x) { return (x + 7u) & ~7ull; }
+constexpr uint64_t align16(uint64_t x) { return (x + 15u) & ~15ull; }
 
 // ---- mirsha_staging.hip
 // The bytes to hash, as the packed arena [0, total).

@@ -1,0 +1,83 @@
+// mirsha_expect.hip — the select kernel of the mixed hash-and-verify ring
+// submissions (mirsha_submit_*_expect, mirsha_async.hip).  A translation unit
+// of its own: the hashing kernels' sources and code object are untouched.
+#include <hip/hip_ext.h>
+
+#include "mirsha_ctx.h"
+
+namespace mirsha {
+
+// A Ready() cycle whose requests may or may not carry the digest their origin
+// expects: has[] marks the requests that do, row base[w] + popcount(has[w]
+// below the lane) of `want` is such a request's expectation
+// (mirsha_expect_plan).  One lane per request, one wave per bitmap word, as
+// verify_digests_kernel.  A lane whose bit is set compares its digest with its
+// expectation row (set lanes map to consecutive rows); the wave's ballot is
+// the mismatch word.  A request without an expectation and every mismatch
+// stores its 32-byte digest row to row i of `out` (host-visible page-locked
+// memory: only these rows cross PCIe); a match stores nothing.  Lane 0 stores
+// the mismatch word and a wave with mismatches adds their number to *count
+// with one atomic.  Waves that start at or beyond n do nothing.
+__global__ __launch_bounds__(kBlockThreads) void expect_select_kernel(const uint4* __restrict__ dig,
+                                                                      const uint4* __restrict__ want,
+                                                                      const unsigned long long* __restrict__ has,
+                                                                      const uint32_t* __restrict__ base, uint32_t n,
+                                                                      uint4* __restrict__ out,
+                                                                      unsigned long long* __restrict__ bits,
+                                                                      uint32_t* __restrict__ count) {
+    const uint64_t i = (uint64_t)blockIdx.x * kBlockThreads + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (i - lane >= n) return;  // the whole wave: no word of the bitmap
+    const uint64_t w = i >> 6;
+    const unsigned long long h = has[w];
+    const bool in = i < n;
+    const bool mine = in && ((h >> lane) & 1ull) != 0ull;
+    uint4 a0 = make_uint4(0u, 0u, 0u, 0u), a1 = a0;
+    if (in) {
+        a0 = dig[2u * i];
+        a1 = dig[2u * i + 1u];
+    }
+    bool differs = false;
+    if (mine) {
+        const uint64_t k = (uint64_t)base[w] + (uint32_t)__popcll(h & ((1ull << lane) - 1ull));
+        const uint4 b0 = want[2u * k], b1 = want[2u * k + 1u];
+        differs = (((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w)) |
+                   ((a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w))) != 0u;
+    }
+    const unsigned long long mis = __ballot(differs);
+    if (in && (!mine || differs)) {  // keep = ~has | mis, below n
+        out[2u * i] = a0;
+        out[2u * i + 1u] = a1;
+    }
+    if (lane == 0u) {
+        bits[w] = mis;
+        if (mis) atomicAdd(count, (uint32_t)__popcll(mis));
+    }
+}
+
+// Launched as every kernel of the library is (launch_k, mirsha_kernels.hip):
+// with the thread's pending timing events bound to the dispatch when a timed
+// launch set them.
+hipError_t launch_expect_select(const uint8_t* digests, const uint8_t* expected, const uint64_t* has,
+                                const uint32_t* base, uint32_t n, uint8_t* out, uint64_t* bits, uint32_t* count,
+                                hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint32_t grid = (uint32_t)(((uint64_t)n + kBlockThreads - 1u) / kBlockThreads);
+    const uint4* d = reinterpret_cast<const uint4*>(digests);
+    const uint4* e = reinterpret_cast<const uint4*>(expected);
+    const unsigned long long* h = reinterpret_cast<const unsigned long long*>(has);
+    uint4* o = reinterpret_cast<uint4*>(out);
+    unsigned long long* b = reinterpret_cast<unsigned long long*>(bits);
+    LaunchEvents& ev = next_launch_events();
+    if (ev.start && ev.stop) {
+        const hipEvent_t e0 = ev.start, e1 = ev.stop;
+        ev = LaunchEvents{};
+        hipExtLaunchKernelGGL(expect_select_kernel, dim3(grid), dim3(kBlockThreads), 0, s, e0, e1, 0u, d, e, h, base, n,
+                              o, b, count);
+    } else {
+        expect_select_kernel<<<grid, kBlockThreads, 0, s>>>(d, e, h, base, n, o, b, count);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace mirsha

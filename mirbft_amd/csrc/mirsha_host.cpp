@@ -714,3 +714,41 @@ extern "C" int mirsha_dedup_plan(const uint8_t* const* slice_ptr, const uint64_t
     if (n_unique_out) *n_unique_out = u;
     return MIRSHA_OK;
 }
+
+// One pass over expect_of, in parallel for a large cycle (2^20 indices: ~0.6 ms
+// serially, on the submitting thread ahead of the DMA): each part checks its
+// indices (the first against its predecessor in the part before) and ORs whole
+// words into the bitmap -- only a part's first and last word can be shared.
+extern "C" int mirsha_expect_plan(const uint32_t* expect_of, uint32_t m, uint32_t n, uint64_t* has_out,
+                                  uint32_t* base_out) {
+    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) >> 6);
+    if (m > n || (m && !expect_of) || (words && (!has_out || !base_out))) return MIRSHA_EINVAL;
+    for (uint32_t w = 0; w < words; w++) has_out[w] = 0;
+    const int T = m < (1u << 17) ? 1 : std::min<int>(mirsha::host::max_threads(), (int)(m >> 16));
+    std::atomic<bool> bad{false};
+    mirsha::host::parallel_for(m, T, [&](uint32_t a, uint32_t b) {
+        uint32_t cur = UINT32_MAX;  // the word being gathered
+        uint64_t acc = 0;
+        for (uint32_t k = a; k < b; k++) {
+            const uint32_t i = expect_of[k];
+            if (i >= n || (k && i <= expect_of[k - 1])) {  // strictly increasing, each < n
+                bad.store(true, std::memory_order_relaxed);
+                return;
+            }
+            if ((i >> 6) != cur) {
+                if (acc) __atomic_fetch_or(&has_out[cur], acc, __ATOMIC_RELAXED);
+                cur = i >> 6;
+                acc = 0;
+            }
+            acc |= 1ull << (i & 63u);
+        }
+        if (acc) __atomic_fetch_or(&has_out[cur], acc, __ATOMIC_RELAXED);
+    });
+    if (bad.load()) return MIRSHA_EINVAL;
+    uint32_t rows = 0;
+    for (uint32_t w = 0; w < words; w++) {
+        base_out[w] = rows;
+        rows += (uint32_t)__builtin_popcountll(has_out[w]);
+    }
+    return MIRSHA_OK;
+}

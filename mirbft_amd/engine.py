@@ -22,6 +22,7 @@ KERNEL_CHAIN = 3
 KERNEL_FUSED = 4
 KERNEL_OVERLAP = 5
 KERNEL_VERIFY = 6
+KERNEL_EXPECT = 7
 ASYNC_SLOTS = 4  # submissions in flight per context (mirsha_submit_slices)
 
 # mirsha_pipeline modes (include/mirsha.h)
@@ -99,6 +100,30 @@ class Ticket:
         self.out = out
 
 
+class ExpectTicket(Ticket):
+    """A submission of Engine.submit_slices_expect / submit_batch_expect.
+    ``has[i]``: request i carried an expectation.  After ``wait`` (or a ``poll``
+    that reports done) ``mismatches`` holds the sorted indices whose digest
+    differs from their expectation, and ``out[i]`` the digest of every request
+    without an expectation and of every mismatch; the row of a matching
+    request is NOT written (its digest equals the expectation passed in)."""
+
+    def __init__(self, value: int, out: np.ndarray, has: np.ndarray, bits: np.ndarray, count: np.ndarray,
+                 short: np.ndarray):
+        super().__init__(value, out)
+        self.has = has
+        self.mismatches: np.ndarray | None = None
+        self._bits, self._count, self._short = bits, count, short
+
+    def _resolve(self) -> None:
+        if self.mismatches is not None:
+            return
+        bad = mismatch_indices(self._bits, self.has.size)
+        if bad.size != int(self._count[0]):
+            raise MirshaError(_lib.MIRSHA_EHIP, f"expect: bitmap has {bad.size} bits set, count is {self._count[0]}")
+        self.mismatches = np.union1d(bad, self._short) if self._short.size else bad
+
+
 def _out_rows(out, n: int) -> np.ndarray:
     """A caller-supplied (n, 32) uint8 result array (checked), or a new one."""
     if out is None:
@@ -139,6 +164,30 @@ def _expected_rows(expected, n: int) -> tuple[np.ndarray, np.ndarray]:
         rows[i] = bytes(32)
     arr = np.frombuffer(b"".join(bytes(d) for d in rows), dtype=np.uint8).reshape(n, 32)
     return arr, np.asarray(bad, dtype=np.int64)
+
+
+def expect_plan(expected) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Host-only: the expectation arguments of a mixed submission
+    (mirsha_submit_*_expect) from one ``Optional[bytes]`` per request.  Returns
+    (expect_of, rows, short): the uint32 indices of the requests that carry an
+    expectation, their (m, 32) uint8 rows, and the indices whose expectation is
+    not 32 bytes long -- a mismatch already on the host (bytes.Equal of unequal
+    lengths), sent to the device as 32 zero bytes (the ``_expected_rows`` rule)."""
+    expected = list(expected)
+    of = [i for i, e in enumerate(expected) if e is not None]
+    rows, short = _expected_rows([expected[i] for i in of], len(of))
+    return np.asarray(of, dtype=np.uint32), rows, np.asarray([of[int(k)] for k in short], dtype=np.int64)
+
+
+def expect_bitmap(expect_of, n: int) -> tuple[np.ndarray, np.ndarray]:
+    """Host-only mirsha_expect_plan: (has, base) -- the ceil(n/64)-word bitmap of
+    the requests listed in ``expect_of`` and the set bits before each word."""
+    of = np.ascontiguousarray(expect_of, dtype=np.uint32)
+    words = (int(n) + 63) // 64
+    has = np.zeros(words, dtype=np.uint64)
+    base = np.zeros(words, dtype=np.uint32)
+    check(_lib.load().mirsha_expect_plan(_ptr(of), of.size, int(n), _ptr(has), _ptr(base)))
+    return has, base
 
 
 def dedup_plan(requests) -> tuple[np.ndarray, int]:
@@ -327,6 +376,52 @@ class Engine:
         self._retire(t.value - ASYNC_SLOTS)
         return Ticket(t.value, out)
 
+    def _expect_ticket(self, submit, n: int, expected, out, keep) -> "ExpectTicket":
+        """One mirsha_submit_*_expect call (``submit(expect_of, rows, m, out,
+        bits, count, ticket_ref)``) and its ticket."""
+        expected = list(expected)
+        if len(expected) != n:
+            raise ValueError(f"{len(expected)} expectations for {n} requests")
+        of, rows, short = expect_plan(expected)
+        has = np.zeros(n, dtype=bool)
+        has[of] = True
+        out = _out_rows(out, n)
+        bits = np.zeros((n + 63) // 64, dtype=np.uint64)
+        count = np.zeros(1, dtype=np.uint32)
+        t = ctypes.c_uint64(0)
+        self._check(submit(_ptr(of), _ptr(rows), int(of.size), _ptr(out), _ptr(bits), count.ctypes.data,
+                           ctypes.byref(t)))
+        # everything the library may still read or write until the ticket retires
+        self._outstanding[t.value] = (out, bits, count, of, rows, keep)
+        self._retire(t.value - ASYNC_SLOTS)
+        return ExpectTicket(t.value, out, has, bits, count, short)
+
+    def submit_slices_expect(self, requests, expected, out=None) -> "ExpectTicket":
+        """submit_slices for a cycle whose requests may carry the digest their
+        origin expects (mirsha_submit_slices_expect): ``expected[i]`` is None or
+        request i's expectation.  ONE ring submission; the compare runs on the
+        device behind the hashing kernel.  See ExpectTicket for what comes back."""
+        sl = requests if isinstance(requests, SliceArrays) else SliceArrays.from_requests(requests)
+        return self._expect_ticket(
+            lambda of, rows, m, o, bits, count, t: self._lib.mirsha_submit_slices_expect(
+                self.ctx, sl.ptr_p, sl.len_p, sl.first_p, sl.n, of, rows, m, o, bits, count, 0, t),
+            sl.n, expected, out, sl)
+
+    def submit_batch_expect(self, arena, off, length, expected, out=None) -> "ExpectTicket":
+        """submit_batch with expectations (mirsha_submit_batch_expect): a
+        page-locked, 16-byte aligned ``out`` receives the kept rows from the
+        select kernel itself."""
+        a = _as_u8(arena)
+        o = np.ascontiguousarray(off, dtype=np.uint64)
+        ln = np.ascontiguousarray(length, dtype=np.uint32)
+        if o.shape != ln.shape:
+            raise ValueError("off and len differ in length")
+        n = int(o.size)
+        return self._expect_ticket(
+            lambda of, rows, m, dst, bits, count, t: self._lib.mirsha_submit_batch_expect(
+                self.ctx, _ptr(a), a.size, _ptr(o), _ptr(ln), n, of, rows, m, dst, bits, count, t),
+            n, expected, out, a)
+
     def _retire(self, upto: int) -> None:
         for k in [k for k in self._outstanding if k <= upto]:
             del self._outstanding[k]
@@ -334,6 +429,8 @@ class Engine:
     def wait(self, ticket: "Ticket") -> np.ndarray:
         self._check(self._lib.mirsha_wait(self.ctx, ticket.value))
         self._retire(ticket.value)
+        if isinstance(ticket, ExpectTicket):
+            ticket._resolve()
         return ticket.out
 
     def poll(self, ticket: "Ticket") -> bool:
@@ -341,6 +438,8 @@ class Engine:
         self._check(self._lib.mirsha_poll(self.ctx, ticket.value, ctypes.byref(done)))
         if done.value:
             self._retire(ticket.value)
+            if isinstance(ticket, ExpectTicket):
+                ticket._resolve()
         return bool(done.value)
 
     def hash_requests_then_batches(self, arena, off, length, idx, batch_first, out=None, batch_out=None):
@@ -765,7 +864,10 @@ __all__ = [
     "CheckpointChains",
     "SliceArrays",
     "Ticket",
+    "ExpectTicket",
     "dedup_plan",
+    "expect_plan",
+    "expect_bitmap",
     "Pipeline",
     "bucket_order",
     "device_count",
@@ -778,6 +880,7 @@ __all__ = [
     "KERNEL_FUSED",
     "KERNEL_OVERLAP",
     "KERNEL_VERIFY",
+    "KERNEL_EXPECT",
     "mismatch_indices",
     "PIPELINE_SEQUENTIAL",
     "PIPELINE_FUSED",

@@ -26,13 +26,19 @@ in origin order, after the caller's other work for the cycle.
 ``verify_on_device=True``: a HashRequest that carries the digest its origin
 expects (``expected``: RequestAck.Digest of a VerifyRequest,
 state_machine.go:408-417; ExpectedDigest of a VerifyBatch,
-batch_tracker.go:139-174) is hashed AND compared on the device
-(``Engine.verify_slices``), and only a verdict comes back: a match yields
-``digest = expected``, the few mismatches are hashed again with
-``hash_slices`` so the caller still sees the true digest.  ``process()``
-returns the same ActionResults with the flag on or off.  ``submit()`` is
-unchanged by the flag: the asynchronous ring has no verify form and always
-hashes.
+batch_tracker.go:139-174) is hashed AND compared on the device, and only a
+verdict comes back for it: a match yields ``digest = expected``, a mismatch
+its true digest.  The results are the same ActionResults with the flag on or
+off.  ``submit()`` (and so ``ProcessorWorkPool.process``) makes ONE ring
+submission for the whole cycle, whatever it holds
+(``Engine.submit_slices_expect``: the compare runs behind the hashing kernel,
+and the digests of the requests without an expectation and of the mismatches
+come back with the verdict); with ``dedup=True`` as well, the requests that
+carry an expectation go in one such submission and the rest in one
+``submit_slices(dedup=True)``.  ``process()`` keeps its synchronous split
+(``Engine.verify_slices`` for the requests with an expectation,
+``hash_slices`` for the rest and, again, for the mismatches): above 32 MiB it
+takes the pipelined staging route, which the ring does not have.
 """
 from __future__ import annotations
 
@@ -107,17 +113,48 @@ def _results(reqs, digests) -> ActionResults:
 class PendingResults:
     """Hash results of one submitted cycle; ``wait()`` returns its ActionResults."""
 
-    def __init__(self, engine: Engine, reqs, ticket):
+    def __init__(self, engine: Engine, reqs, ticket, parts=None):
+        """``ticket``: the cycle's one submission, or None; ``parts`` instead:
+        [(ticket, request indices)] of a cycle split over several submissions."""
         self._engine, self._reqs, self._ticket = engine, reqs, ticket
+        self._parts = parts
         self._results: Optional[ActionResults] = None
 
+    def _tickets(self):
+        if self._parts is not None:
+            return [t for t, _ in self._parts]
+        return [] if self._ticket is None else [self._ticket]
+
     def done(self) -> bool:
-        return self._results is not None or self._ticket is None or self._engine.poll(self._ticket)
+        return self._results is not None or all(self._engine.poll(t) for t in self._tickets())
+
+    def _part(self, ticket, idx, digests) -> None:
+        """digests[idx[k]] = request k of one submission.  A mixed submission
+        (``ticket.has``): a matching request's digest is its expectation (its
+        row of ``out`` is not written), every other request's is its row."""
+        out = self._engine.wait(ticket)
+        has = getattr(ticket, "has", None)
+        if has is None:
+            for k, i in enumerate(idx):
+                digests[i] = out[k].tobytes()
+            return
+        wrong = set(int(k) for k in ticket.mismatches)
+        for k, i in enumerate(idx):
+            match = bool(has[k]) and k not in wrong
+            digests[i] = bytes(self._reqs[i].expected) if match else out[k].tobytes()
 
     def wait(self) -> ActionResults:
         if self._results is None:
-            digests = self._engine.wait(self._ticket) if self._ticket is not None else []
-            self._results = _results(self._reqs, digests)
+            reqs = self._reqs
+            parts = self._parts
+            if parts is None:
+                parts = [] if self._ticket is None else [(self._ticket, range(len(reqs)))]
+            digests: list = [None] * len(reqs)
+            for ticket, idx in parts:
+                self._part(ticket, idx, digests)
+            # Digests[i] for actions.Hash[i] (processor.go:139)
+            self._results = ActionResults(digests=[HashResult(digest=digests[i], request=r)
+                                                   for i, r in enumerate(reqs)])
         return self._results
 
 
@@ -159,11 +196,28 @@ class Processor:
 
     def submit(self, actions: Actions) -> PendingResults:
         """Asynchronous process(): queue the cycle's hashing, return at once.
-        Always hashes (``verify_on_device`` does not apply: the ring has no
-        verify form)."""
+        With ``verify_on_device`` the whole cycle is ONE mixed submission
+        (``submit_slices_expect``); with ``dedup`` as well, the requests that
+        carry an expectation are one such submission and the rest one
+        ``submit_slices(dedup=True)`` (the two do not combine in one)."""
         reqs = list(actions.hash)
-        ticket = self.engine.submit_slices([r.data for r in reqs], dedup=self.dedup) if reqs else None
-        return PendingResults(self.engine, reqs, ticket)
+        if not reqs:
+            return PendingResults(self.engine, reqs, None)
+        if not self.verify_on_device:
+            return PendingResults(self.engine, reqs, self.engine.submit_slices([r.data for r in reqs],
+                                                                               dedup=self.dedup))
+        if not self.dedup:
+            return PendingResults(self.engine, reqs, self.engine.submit_slices_expect(
+                [r.data for r in reqs], [r.expected for r in reqs]))
+        check = [i for i, r in enumerate(reqs) if r.expected is not None]
+        plain = [i for i, r in enumerate(reqs) if r.expected is None]
+        parts = []
+        if check:
+            parts.append((self.engine.submit_slices_expect([reqs[i].data for i in check],
+                                                           [reqs[i].expected for i in check]), check))
+        if plain:
+            parts.append((self.engine.submit_slices([reqs[i].data for i in plain], dedup=True), plain))
+        return PendingResults(self.engine, reqs, None, parts)
 
 
 class ProcessorWorkPool(Processor):
@@ -183,14 +237,10 @@ class ProcessorWorkPool(Processor):
         """processor.go:447-470: the pool hashes while the WAL and the sends
         proceed.  Here the cycle's hashing is submitted first, ``overlap()``
         (the caller's persist / transmit work) runs while the GPU hashes, then
-        the digests are collected in origin order.  With ``verify_on_device``
-        the cycle goes through the synchronous split of ``Processor.process``
-        (``overlap()`` runs first: the verify calls are synchronous)."""
+        the digests are collected in origin order -- with ``verify_on_device``
+        too: the cycle's one mixed submission (``Processor.submit``) keeps the
+        overlap."""
         with self._mutex:  # processor.go:448-449
-            if self.verify_on_device:
-                if overlap is not None:
-                    overlap()
-                return Processor.process(self, actions)
             pending = self.submit(actions)
             if overlap is not None:
                 overlap()

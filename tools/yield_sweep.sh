@@ -20,7 +20,7 @@ if [ "${1:-}" = "build" ]; then
         mkdir -p tools/ablib/y$f
         (cd "$d/m/csrc" && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -shared \
             -o "$OLDPWD/tools/ablib/y$f/libmirsha.so" mirsha_kernels.hip mirsha_api.hip mirsha_staging.hip \
-            mirsha_plan.hip mirsha_async.hip mirsha_multi.hip mirsha_scan.hip mirsha_host.cpp) &
+            mirsha_plan.hip mirsha_async.hip mirsha_expect.hip mirsha_multi.hip mirsha_scan.hip mirsha_host.cpp) &
     done
     wait
     ls -la tools/ablib/*/libmirsha.so
