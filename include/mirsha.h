@@ -500,6 +500,75 @@ int mirsha_chains_absorb(mirsha_ctx* ctx, mirsha_chains* chains, const uint8_t* 
 int mirsha_chains_sum(mirsha_ctx* ctx, mirsha_chains* chains, const uint32_t* which, uint32_t k, uint8_t* out);
 int mirsha_chains_reset(mirsha_ctx* ctx, mirsha_chains* chains, const uint32_t* which, uint32_t k);
 
+/* ------------------------------- a cycle's Commits on the chains (one call) */
+/* The commit loop of Processor.Process (processor.go:145-168): every
+ * committed batch is applied to the application log (p.Log.Apply, :147) and
+ * at a checkpoint the log's value goes into ActionResults.Checkpoints
+ * (p.Log.Snap, :163-167).  With the testengine's log that is, per node,
+ * ActiveHash.Write(request.Digest) for each request of each batch
+ * (testengine/recorder.go:222-223) and, at a checkpoint, ActiveHash.Sum(nil)
+ * (:244) followed by a fresh hasher (NodeState.Set, :186-207).  A cycle's
+ * actions.Commits is an ordered mixture of the two; here it is ONE programme
+ * of n_ops ops and ONE kernel launch over the running states.
+ *
+ * Op i acts on chain op_chain[i] (< n_chains); ops of one chain take effect
+ * in op order.  op_digest[i] is
+ *   an index < n_digests: Write(digests[32*idx .. +32)); any number of ops and
+ *     chains may name the same index (N nodes committing one batch), the table
+ *     is uploaded once;
+ *   MIRSHA_NULL_INDEX: a null request's empty digest, a Write that changes
+ *     nothing (as in the digest-list calls);
+ *   MIRSHA_COMMIT_CHECKPOINT: Sum, then reset; the chain goes on with the ops
+ *     that follow. */
+#define MIRSHA_COMMIT_CHECKPOINT 0xFFFFFFFEu
+/* Checkpoint flag of a plan entry; at most this many ops and digests a call. */
+#define MIRSHA_COMMIT_ENTRY_CHECKPOINT 0x80000000u
+
+/* Host-only (no device, no context), like mirsha_dedup_plan /
+ * mirsha_expect_plan: exactly the arrays mirsha_chains_commit sends to the
+ * device (recorder.go:213-256 turned into per-chain programmes).
+ *   act_out[k], k < *n_active_out: the chains with at least one write or
+ *     checkpoint, ascending.  A chain named only by null writes is not
+ *     active: the kernel neither reads nor writes it.
+ *   efirst_out[0 .. n_active]: chain act_out[k] runs entries
+ *     ent_out[efirst_out[k] .. efirst_out[k+1]), in op order, null writes
+ *     removed; efirst_out[0] = 0, efirst_out[n_active] = *n_entries_out.
+ *   ent_out[e]: a digest index (< n_digests), or
+ *     MIRSHA_COMMIT_ENTRY_CHECKPOINT | row, the row of the values output the
+ *     checkpoint's Sum goes to: rows count the checkpoint ops in op order
+ *     across all chains (origin order).
+ *   *n_values_out: the number of checkpoint ops.
+ * Capacities: act_out min(n_ops, n_chains), efirst_out one more, ent_out
+ * n_ops entries.  MIRSHA_EINVAL: a NULL array with a non-zero count, a chain
+ * id >= n_chains, a digest index >= n_digests that is neither marker; then
+ * *bad_op_out (if given) is the first offending op, or UINT32_MAX.
+ * MIRSHA_ERANGE: n_ops or n_digests above MIRSHA_COMMIT_ENTRY_CHECKPOINT.
+ * MIRSHA_ENOMEM: no host memory for the per-chain counters. */
+int mirsha_commit_plan(const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint32_t n_chains,
+                       uint32_t n_digests, uint32_t* act_out, uint32_t* efirst_out, uint32_t* ent_out,
+                       uint32_t* n_active_out, uint32_t* n_entries_out, uint32_t* n_values_out,
+                       uint32_t* bad_op_out);
+
+/* Runs the programme (processor.go:145-168, see above).  values_out gets 32
+ * bytes per checkpoint op, in op order across all chains; *n_values_out is
+ * their number.  Synchronous like the other mirsha_chains_* calls; the state
+ * left behind (midstate, pending digest, count) is the one mirsha_chains_absorb
+ * / _sum / _reset use, so the calls mix freely on one mirsha_chains.  The
+ * launch is timed as kernel id 1.  A validation failure (MIRSHA_EINVAL, the
+ * message names the op; chains of another device) launches nothing and leaves
+ * every state untouched.  n_ops == 0: MIRSHA_OK, *n_values_out = 0. */
+int mirsha_chains_commit(mirsha_ctx* ctx, mirsha_chains* chains, const uint8_t* digests, uint32_t n_digests,
+                         const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
+                         uint32_t* n_values_out);
+/* The same with the digest table in device memory (16-byte aligned), e.g. the
+ * d_req_out a cycle's request hashing wrote: requests -> batches -> commits
+ * without the digests leaving the GPU.  The table is read on the context's
+ * stream, behind whatever was queued there.  The ops are host arrays and
+ * values_out is host memory, as above. */
+int mirsha_chains_commit_device(mirsha_ctx* ctx, mirsha_chains* chains, const uint8_t* d_digests, uint32_t n_digests,
+                                const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
+                                uint8_t* values_out, uint32_t* n_values_out);
+
 /* ------------------------------------------------- multi-GPU (one process) */
 /* Shards the n requests by contiguous range across ndev devices (balanced by
  * block count), one context per device, host gather into origin order.  No

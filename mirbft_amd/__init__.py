@@ -7,10 +7,12 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 """
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
-from .engine import (CheckpointChains, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order, dedup_plan,
-                     device_count, expect_bitmap, expect_plan, hash_batch_multi, mismatch_indices)
-from .processor import (ActionResults, Actions, GpuHash, HashRequest, HashResult, PendingResults, Processor,
-                        ProcessorWorkPool, gpu_hasher)
+from .engine import (CheckpointChains, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order,
+                     commit_plan, dedup_plan, device_count, expect_bitmap, expect_plan, hash_batch_multi,
+                     mismatch_indices)
+from .processor import (ActionResults, Actions, Checkpoint, CheckpointResult, Commit, CommitBatch, DeviceLog, GpuHash,
+                        HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, commit_programme,
+                        gpu_hasher)
 
 __all__ = [
     "Engine",
@@ -21,6 +23,13 @@ __all__ = [
     "dedup_plan",
     "expect_plan",
     "expect_bitmap",
+    "commit_plan",
+    "commit_programme",
+    "Checkpoint",
+    "CheckpointResult",
+    "Commit",
+    "CommitBatch",
+    "DeviceLog",
     "PendingResults",
     "MirshaError",
     "MirshaUnavailable",

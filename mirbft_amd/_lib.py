@@ -21,6 +21,8 @@ MIRSHA_ENOMEM = -3
 MIRSHA_ERANGE = -4
 MIRSHA_ENODEV = -5
 MIRSHA_NULL_INDEX = 0xFFFFFFFF
+MIRSHA_COMMIT_CHECKPOINT = 0xFFFFFFFE
+MIRSHA_COMMIT_ENTRY_CHECKPOINT = 0x80000000
 MIRSHA_MAX_MESSAGE_BYTES = 0xFFFFFF00
 MIRSHA_MAX_DEVICE_ARENA_BYTES = 0xFFFFFF00
 MIRSHA_SUBMIT_DEDUP = 1
@@ -129,6 +131,18 @@ SIGNATURES = {
     "mirsha_chains_absorb": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     "mirsha_chains_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "mirsha_chains_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
+    "mirsha_commit_plan": (
+        c_int,
+        [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, _u32p, _u32p, _u32p, _u32p],
+    ),
+    "mirsha_chains_commit": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, _u32p],
+    ),
+    "mirsha_chains_commit_device": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, _u32p],
+    ),
     "mirsha_hash_batch_multi": (
         c_int,
         [c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p],

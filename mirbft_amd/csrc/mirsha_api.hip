@@ -353,7 +353,7 @@ void mirsha_chains_destroy(mirsha_chains* ch) {
     if (!ch) return;
     (void)hipSetDevice(ch->device);
     for (DevBuf* b : {&ch->d_h, &ch->d_pend, &ch->d_cnt, &ch->d_dig, &ch->d_pos, &ch->d_act, &ch->d_afirst,
-                      &ch->d_which, &ch->d_out})
+                      &ch->d_which, &ch->d_out, &ch->d_plan})
         b->release();
     delete ch;
 }
@@ -441,6 +441,76 @@ int mirsha_chains_reset(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which,
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MIRSHA_OK;
+}
+
+namespace {
+static_assert(mirsha::kCommitEntryCheckpoint == MIRSHA_COMMIT_ENTRY_CHECKPOINT, "plan entry flag");
+
+// Both forms of mirsha_chains_commit: the plan (every check, on the host,
+// before anything is queued), the digest table (uploaded once if it is host
+// memory), the plan block in one copy, one launch, the values back.
+static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
+                  const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
+                  uint32_t* n_values_out) {
+    if (!c || !ch || !n_values_out) return MIRSHA_EINVAL;
+    *n_values_out = 0;
+    if (n_ops == 0) return MIRSHA_OK;
+    if (!op_chain || !op_digest) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (n_digests && !digests) return fail(c, MIRSHA_EINVAL, "NULL digest table (%u digests)", n_digests);
+    if (on_device && (reinterpret_cast<uintptr_t>(digests) & 15u))
+        return fail(c, MIRSHA_EINVAL, "d_digests must be 16-byte aligned");
+    if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
+    const uint32_t cap = std::min(n_ops, ch->n);  // active chains at most
+    const size_t o_first = cap, o_ent = 2ull * cap + 1u;
+    ch->plan.resize(o_ent + n_ops);
+    uint32_t* plan = ch->plan.data();
+    uint32_t na = 0, entries = 0, values = 0, bad = UINT32_MAX;
+    const int rc = mirsha_commit_plan(op_chain, op_digest, n_ops, ch->n, n_digests, plan, plan + o_first, plan + o_ent,
+                                      &na, &entries, &values, &bad);
+    if (rc == MIRSHA_ERANGE)
+        return fail(c, rc, "%u ops / %u digests > %u", n_ops, n_digests, MIRSHA_COMMIT_ENTRY_CHECKPOINT);
+    if (rc != MIRSHA_OK) {
+        if (bad == UINT32_MAX) return fail(c, rc, "commit plan failed");
+        if (op_chain[bad] >= ch->n) return fail(c, rc, "op_chain[%u] = %u >= %u", bad, op_chain[bad], ch->n);
+        return fail(c, rc, "op_digest[%u] = %u >= %u", bad, op_digest[bad], n_digests);
+    }
+    if (values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u checkpoints)", values);
+    if (na == 0) return MIRSHA_OK;  // null writes only
+    if (int r = use_device(c)) return r;
+    const uint8_t* d_dig = digests;
+    if (!on_device && n_digests) {
+        HIP_TRY(c, ch->d_dig.ensure(32ull * n_digests));
+        HIP_TRY(c, hipMemcpyAsync(ch->d_dig.p, digests, 32ull * n_digests, hipMemcpyHostToDevice, c->stream));
+        d_dig = ch->d_dig.as<uint8_t>();
+    }
+    const size_t plan_bytes = 4ull * (o_ent + entries);
+    HIP_TRY(c, ch->d_plan.ensure(plan_bytes));
+    HIP_TRY(c, ch->d_out.ensure(32ull * values));
+    HIP_TRY(c, hipMemcpyAsync(ch->d_plan.p, plan, plan_bytes, hipMemcpyHostToDevice, c->stream));
+    const uint32_t* d_plan = ch->d_plan.as<uint32_t>();
+    if (int r = timed_launch(c, 1, [&] {
+            return mirsha::launch_chains_commit(d_dig, d_plan + o_ent, d_plan, d_plan + o_first, na,
+                                                ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(),
+                                                ch->d_cnt.as<uint64_t>(), ch->d_out.as<uint8_t>(), c->stream);
+        }))
+        return r;
+    if (values) HIP_TRY(c, hipMemcpyAsync(values_out, ch->d_out.p, 32ull * values, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // ch->plan and the caller's table feed async copies
+    *n_values_out = values;
+    return MIRSHA_OK;
+}
+}  // namespace
+
+int mirsha_chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, uint32_t n_digests,
+                         const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
+                         uint32_t* n_values_out) {
+    return chains_commit(c, ch, digests, false, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
+}
+
+int mirsha_chains_commit_device(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* d_digests, uint32_t n_digests,
+                                const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
+                                uint8_t* values_out, uint32_t* n_values_out) {
+    return chains_commit(c, ch, d_digests, true, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
 }
 
 int mirsha_ctx_host_profile(const mirsha_ctx* c, double* ms_out, int n) {

@@ -222,6 +222,10 @@ struct mirsha_chains {
     uint32_t n = 0;
     DevBuf d_h, d_pend, d_cnt;                        // state
     DevBuf d_dig, d_pos, d_act, d_afirst, d_which, d_out;  // per call
+    // mirsha_chains_commit: mirsha_commit_plan's arrays in one block
+    // [act | efirst | ent], one H2D copy (kept across calls).
+    std::vector<uint32_t> plan;
+    DevBuf d_plan;
 };
 
 // A request -> batch-digest pipeline plan (see mirsha.h, mirsha_pipeline_create).

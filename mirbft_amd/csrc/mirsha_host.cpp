@@ -12,6 +12,7 @@
 #include <condition_variable>
 #include <map>
 #include <mutex>
+#include <new>
 #include <thread>
 #include <unordered_map>
 #include <vector>
@@ -750,5 +751,63 @@ extern "C" int mirsha_expect_plan(const uint32_t* expect_of, uint32_t m, uint32_
         base_out[w] = rows;
         rows += (uint32_t)__builtin_popcountll(has_out[w]);
     }
+    return MIRSHA_OK;
+}
+
+// A cycle's commit programme (mirsha_chains_commit) grouped by chain: a
+// validating pass (nothing is written before every op has passed), a count of
+// each chain's entries (null writes dropped), the active chains and their
+// ranges, then a stable scatter in op order (a counting sort, as
+// mirsha_chains_absorb groups its writes).  Checkpoint rows count the
+// checkpoint ops in op order across all chains.
+extern "C" int mirsha_commit_plan(const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
+                                  uint32_t n_chains, uint32_t n_digests, uint32_t* act_out, uint32_t* efirst_out,
+                                  uint32_t* ent_out, uint32_t* n_active_out, uint32_t* n_entries_out,
+                                  uint32_t* n_values_out, uint32_t* bad_op_out) {
+    if (bad_op_out) *bad_op_out = UINT32_MAX;
+    if (!n_active_out || !n_entries_out || !n_values_out) return MIRSHA_EINVAL;
+    *n_active_out = *n_entries_out = *n_values_out = 0;
+    if (n_ops > MIRSHA_COMMIT_ENTRY_CHECKPOINT || n_digests > MIRSHA_COMMIT_ENTRY_CHECKPOINT) return MIRSHA_ERANGE;
+    if (n_ops == 0) {
+        if (efirst_out) efirst_out[0] = 0;
+        return MIRSHA_OK;
+    }
+    if (!op_chain || !op_digest) return MIRSHA_EINVAL;
+    for (uint32_t i = 0; i < n_ops; i++) {
+        const uint32_t d = op_digest[i];
+        const bool marker = d == MIRSHA_NULL_INDEX || d == MIRSHA_COMMIT_CHECKPOINT;
+        if (op_chain[i] >= n_chains || (!marker && d >= n_digests)) {
+            if (bad_op_out) *bad_op_out = i;
+            return MIRSHA_EINVAL;
+        }
+    }
+    if (!act_out || !efirst_out || !ent_out) return MIRSHA_EINVAL;
+    std::vector<uint32_t> at;  // entries of chain c, then where its next entry goes
+    try {
+        at.assign((size_t)n_chains, 0);
+    } catch (const std::bad_alloc&) {
+        return MIRSHA_ENOMEM;
+    }
+    for (uint32_t i = 0; i < n_ops; i++)
+        if (op_digest[i] != MIRSHA_NULL_INDEX) at[op_chain[i]]++;
+    uint32_t na = 0, total = 0;
+    efirst_out[0] = 0;
+    for (uint32_t c = 0; c < n_chains; c++) {
+        const uint32_t m = at[c];
+        at[c] = total;
+        if (!m) continue;
+        act_out[na++] = c;
+        total += m;
+        efirst_out[na] = total;
+    }
+    uint32_t rows = 0;
+    for (uint32_t i = 0; i < n_ops; i++) {
+        const uint32_t d = op_digest[i];
+        if (d == MIRSHA_NULL_INDEX) continue;
+        ent_out[at[op_chain[i]]++] = d == MIRSHA_COMMIT_CHECKPOINT ? (MIRSHA_COMMIT_ENTRY_CHECKPOINT | rows++) : d;
+    }
+    *n_active_out = na;
+    *n_entries_out = total;
+    *n_values_out = rows;
     return MIRSHA_OK;
 }

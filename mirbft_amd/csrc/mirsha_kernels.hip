@@ -2514,6 +2514,150 @@ __global__ __launch_bounds__(kBlockThreads) void chains_reset_kernel(const uint3
     cnt[c] = 0u;
 }
 
+// ---- a cycle's Commits in one launch (processor.go:145-168) -----------------
+// The commit loop of Processor.Process applies every committed batch to the
+// application log and takes the log's value at each checkpoint; with the
+// testengine's log (NodeState.Commit, testengine/recorder.go:213-256) that is
+// a programme of Write(digest) and Sum-then-fresh-hasher per node.  One lane
+// per chain that has entries this cycle (mirsha_commit_plan): entries
+// ent[efirst[k] .. efirst[k+1]) in op order, null writes already removed.  An
+// entry below kCommitEntryCheckpoint is a row of the shared digest table to
+// write; otherwise its low 31 bits are the output row of a checkpoint.
+//
+// A step is at most one compression per lane: two whole digests (the first
+// may be the digest pending from earlier writes), or the final padded block
+// of a checkpoint (pending digest, if any, 0x80, bit length: always one
+// block), after which the lane's state is Hasher() again.  A lone last write
+// becomes the pending digest without a compression.  The state left behind is
+// chains_absorb_kernel's, so the calls mix freely on one mirsha_chains.
+//
+// Which entries a step consumes depends on the entry kinds and the parity
+// only, never on a hash value, so the lane's walk over its programme
+// (commit_fetch) runs one step ahead of the hashing: the next step's entries
+// were loaded a step earlier, its digest rows are requested before this
+// step's compression and first touched (byte swap) after it.  A lone lane
+// then pays max(compression, one load) per step, not their sum.
+struct CommitStep {
+    uint4 a0, a1, b0, b1;  // raw rows of the two halves (zeros where the step loads none)
+    uint64_t bits;         // checkpoint: the message's bit length
+    uint32_t row;          // checkpoint: output row
+    bool use_pend;         // first half = the pending digest
+    bool have_a;           // checkpoint: a first half precedes the 0x80
+    bool write, cp;        // compress two digests / the final block (neither: nothing to hash)
+    bool keep;             // a lone last write: the first half becomes the pending digest
+};
+
+// Plans step t of a lane at entry e (x0 = ent[e], xn = ent[e + 1], each
+// loaded only below `end`), requests its digest rows, moves e and the digest
+// count n past it and loads the entries of step t + 1.  Every load is guarded
+// by the lane's own range: past `end` the index would run into the next
+// chain's entries or beyond the array (the note on pos in
+// chains_absorb_kernel).
+__device__ __forceinline__ CommitStep commit_fetch(const uint8_t* __restrict__ digests,
+                                                   const uint32_t* __restrict__ ent, uint32_t end, uint32_t& e,
+                                                   uint64_t& n, uint32_t& x0, uint32_t& xn) {
+    CommitStep s;
+    const bool live = e < end;
+    const bool odd = (n & 1u) != 0u;
+    const bool take0 = live && !odd && !(x0 & kCommitEntryCheckpoint);  // first half from the table
+    const uint32_t e1 = e + (take0 ? 1u : 0u);
+    const bool live1 = live && e1 < end;  // odd && live: e1 == e, so live1
+    const uint32_t x1 = take0 ? xn : x0;
+    s.write = live1 && !(x1 & kCommitEntryCheckpoint);
+    s.cp = live1 && (x1 & kCommitEntryCheckpoint) != 0u;
+    s.use_pend = odd && live1;
+    s.have_a = odd || take0;
+    s.keep = take0 && !live1;
+    s.row = x1 & ~kCommitEntryCheckpoint;
+    s.bits = (n + (take0 ? 1u : 0u)) * 256u;
+    s.a0 = s.a1 = s.b0 = s.b1 = make_uint4(0u, 0u, 0u, 0u);
+    if (take0) {
+        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x0);
+        s.a0 = d[0];
+        s.a1 = d[1];
+    }
+    if (s.write) {
+        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x1);
+        s.b0 = d[0];
+        s.b1 = d[1];
+    }
+    n = s.cp ? 0u : n + (take0 ? 1u : 0u) + (s.write ? 1u : 0u);
+    e = e1 + (live1 ? 1u : 0u);
+    x0 = e < end ? ent[e] : 0u;
+    xn = e + 1u < end ? ent[e + 1u] : 0u;  // e <= end <= 2^31: no wrap
+    return s;
+}
+
+__device__ __forceinline__ void be_words(const uint4& v, uint32_t w[4]) {
+    w[0] = __builtin_bswap32(v.x); w[1] = __builtin_bswap32(v.y);
+    w[2] = __builtin_bswap32(v.z); w[3] = __builtin_bswap32(v.w);
+}
+
+__global__ __launch_bounds__(kBlockThreads) void chains_commit_kernel(
+    const uint8_t* __restrict__ digests, const uint32_t* __restrict__ ent, const uint32_t* __restrict__ act,
+    const uint32_t* __restrict__ efirst, uint32_t n_active, uint32_t* __restrict__ h, uint32_t* __restrict__ pend,
+    uint64_t* __restrict__ cnt, uint8_t* __restrict__ out) {
+    const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
+    const bool valid = k < n_active;
+    const uint32_t c = valid ? act[k] : 0u;
+    uint32_t e = valid ? efirst[k] : 0u;
+    const uint32_t end = valid ? efirst[k + 1] : 0u;
+    uint32_t st[8], pw[8];
+    uint64_t n = 0;
+    if (valid) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            st[i] = h[8ull * c + i];
+            pw[i] = pend[8ull * c + i];
+        }
+        n = cnt[c];
+    }
+    uint32_t x0 = e < end ? ent[e] : 0u;
+    uint32_t xn = e + 1u < end ? ent[e + 1u] : 0u;
+    CommitStep s = commit_fetch(digests, ent, end, e, n, x0, xn);
+    // Wave-uniform: a lane whose step does nothing has reached its end (only a
+    // programme's last step can be without a compression).
+    while (__ballot(s.write || s.cp || s.keep) != 0ull) {
+        const CommitStep nx = commit_fetch(digests, ent, end, e, n, x0, xn);
+        uint32_t w[16];
+        be_words(s.a0, w); be_words(s.a1, w + 4); be_words(s.b0, w + 8); be_words(s.b1, w + 12);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if (s.use_pend) w[i] = pw[i];
+            if (s.keep) pw[i] = w[i];
+        }
+        if (s.cp) {
+            if (s.have_a) w[8] = 0x80000000u; else w[0] = 0x80000000u;
+            w[14] = (uint32_t)(s.bits >> 32);
+            w[15] = (uint32_t)s.bits;
+        }
+        if (s.write || s.cp) compress_asm_lat(st, w);
+        if (s.cp) {
+            store_digest(out, s.row, st);
+#pragma unroll
+            for (int i = 0; i < 8; i++) st[i] = kH0[i];
+        }
+        s = nx;
+    }
+    if (valid) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            h[8ull * c + i] = st[i];
+            pend[8ull * c + i] = pw[i];
+        }
+        cnt[c] = n;
+    }
+}
+
+hipError_t launch_chains_commit(const uint8_t* digests, const uint32_t* ent, const uint32_t* act,
+                                const uint32_t* efirst, uint32_t n_active, uint32_t* h, uint32_t* pend, uint64_t* cnt,
+                                uint8_t* out, hipStream_t s) {
+    if (n_active == 0) return hipSuccess;
+    launch_k(chains_commit_kernel, (n_active + kBlockThreads - 1u) / kBlockThreads, kBlockThreads, 0, s, digests, ent,
+             act, efirst, n_active, h, pend, cnt, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_chains_absorb(const uint8_t* digests, const uint32_t* pos, const uint32_t* act, const uint32_t* afirst,
                                 uint32_t n_active, uint32_t* h, uint32_t* pend, uint64_t* cnt, hipStream_t s) {
     if (n_active == 0) return hipSuccess;

@@ -13,7 +13,7 @@ from typing import Iterable, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import MIRSHA_NULL_INDEX, MirshaError, check
+from ._lib import MIRSHA_COMMIT_CHECKPOINT, MIRSHA_NULL_INDEX, MirshaError, check
 
 KERNEL_MSGS = 0
 KERNEL_LISTS = 1
@@ -199,6 +199,36 @@ def dedup_plan(requests) -> tuple[np.ndarray, int]:
     rc = _lib.load().mirsha_dedup_plan(sl.ptr_p, sl.len_p, sl.first_p, sl.n, _ptr(rep), ctypes.byref(u))
     check(rc)
     return rep, u.value
+
+
+def _commit_ops(op_chain, op_digest) -> tuple[np.ndarray, np.ndarray]:
+    oc = np.ascontiguousarray(op_chain, dtype=np.uint32).reshape(-1)
+    od = np.ascontiguousarray(op_digest, dtype=np.uint32).reshape(-1)
+    if oc.size != od.size:
+        raise ValueError("one chain id and one digest index (or marker) per op")
+    return oc, od
+
+
+def commit_plan(op_chain, op_digest, n_chains: int, n_digests: int):
+    """Host-only mirsha_commit_plan: the arrays ``CheckpointChains.commit`` sends
+    to the device for a cycle's commit programme.  Returns (act, efirst, ent,
+    n_values): the active chains (ascending), their entry ranges
+    ``ent[efirst[k]:efirst[k+1]]`` in op order with null writes removed -- a
+    digest index, or ``MIRSHA_COMMIT_ENTRY_CHECKPOINT | row`` with the row of
+    the values output -- and the number of checkpoint ops."""
+    oc, od = _commit_ops(op_chain, op_digest)
+    cap = min(oc.size, int(n_chains))
+    act = np.zeros(cap, dtype=np.uint32)
+    efirst = np.zeros(cap + 1, dtype=np.uint32)
+    ent = np.zeros(oc.size, dtype=np.uint32)
+    na, ne, nv, bad = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = _lib.load().mirsha_commit_plan(_ptr(oc), _ptr(od), oc.size, int(n_chains), int(n_digests), _ptr(act),
+                                        efirst.ctypes.data, _ptr(ent), ctypes.byref(na), ctypes.byref(ne),
+                                        ctypes.byref(nv), ctypes.byref(bad))
+    if rc != _lib.MIRSHA_OK:
+        where = f"op {bad.value}" if bad.value != 0xFFFFFFFF else "arguments"
+        raise MirshaError(rc, f"commit plan: {where}")
+    return act[:na.value], efirst[:na.value + 1], ent[:ne.value], nv.value
 
 
 def device_count() -> int:
@@ -697,6 +727,32 @@ class CheckpointChains:
         if w.size:
             self._engine._check(self._lib.mirsha_chains_reset(self._engine.ctx, self.handle, _ptr(w), w.size))
 
+    def commit(self, digests, op_chain, op_digest) -> np.ndarray:
+        """One cycle's commit programme in ONE call (mirsha_chains_commit, the
+        commit loop of processor.go:145-168): op i acts on chain op_chain[i];
+        op_digest[i] is a row of ``digests`` to write, MIRSHA_NULL_INDEX (a
+        null request: nothing) or MIRSHA_COMMIT_CHECKPOINT (Sum, then a fresh
+        hasher).  Returns the checkpoint values, (k, 32) uint8, in op order."""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        return self._commit(self._lib.mirsha_chains_commit, _ptr(d), d.shape[0], op_chain, op_digest)
+
+    def commit_device(self, d_digests: int, n_digests: int, op_chain, op_digest) -> np.ndarray:
+        """commit() with the digest table in device memory (a raw device
+        address, 16-byte aligned; e.g. the output of ``hash_batch_device``).
+        The ops stay host arrays and the values come back to the host."""
+        return self._commit(self._lib.mirsha_chains_commit_device, int(d_digests) or None, int(n_digests), op_chain,
+                            op_digest)
+
+    def _commit(self, call, table, n_digests: int, op_chain, op_digest) -> np.ndarray:
+        oc, od = _commit_ops(op_chain, op_digest)
+        out = np.empty((int(np.count_nonzero(od == _lib.MIRSHA_COMMIT_CHECKPOINT)), 32), dtype=np.uint8)
+        k = ctypes.c_uint32(0)
+        self._engine._check(call(self._engine.ctx, self.handle, table, n_digests, _ptr(oc), _ptr(od), oc.size,
+                                 _ptr(out), ctypes.byref(k)))
+        if k.value != out.shape[0]:
+            raise MirshaError(_lib.MIRSHA_EHIP, f"commit: {k.value} values for {out.shape[0]} checkpoints")
+        return out
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             self._lib.mirsha_chains_destroy(self.handle)
@@ -868,6 +924,8 @@ __all__ = [
     "dedup_plan",
     "expect_plan",
     "expect_bitmap",
+    "commit_plan",
+    "MIRSHA_COMMIT_CHECKPOINT",
     "Pipeline",
     "bucket_order",
     "device_count",

@@ -106,14 +106,87 @@ ActionResults make_results(const std::vector<const HashRequest*>& reqs,
 }
 }  // namespace
 
+DeviceLog::DeviceLog(GpuEngine& engine, uint32_t n_nodes, uint32_t node)
+    : engine_(engine), n_nodes_(n_nodes), node_(node) {
+    if (node >= n_nodes) throw std::runtime_error("DeviceLog: node out of range");
+    int rc = mirsha_chains_create(engine.ctx(), n_nodes, &chains_);
+    if (rc != MIRSHA_OK) panic(engine.ctx(), rc, "could not create the checkpoint chains");
+}
+
+DeviceLog::~DeviceLog() { mirsha_chains_destroy(chains_); }
+
+std::vector<std::array<uint8_t, 32>> DeviceLog::CommitCycle(const std::vector<const Commit*>& commits) {
+    // The cycle as one programme: each non-null request digest once in the
+    // table, each step as n_nodes consecutive ops (node 0 first).
+    std::vector<uint8_t> table;
+    std::vector<uint32_t> prog;
+    for (const Commit* c : commits) {
+        if (!c || (c->Batch == nullptr) == (c->Checkpoint == nullptr))
+            throw std::runtime_error("a Commit is a batch or else a checkpoint");
+        if (c->Checkpoint) {  // value := p.Log.Snap(...) (processor.go:163)
+            prog.push_back(MIRSHA_COMMIT_CHECKPOINT);
+            continue;
+        }
+        for (const Bytes& d : c->Batch->Digests) {  // p.Log.Apply(commit.Batch) (processor.go:147)
+            if (d.size == 0) {
+                prog.push_back(MIRSHA_NULL_INDEX);
+                continue;
+            }
+            if (d.size != 32 || !d.data) throw std::runtime_error("a request digest is 32 bytes, or empty");
+            prog.push_back((uint32_t)(table.size() / 32));
+            table.insert(table.end(), d.data, d.data + 32);
+        }
+    }
+    std::vector<uint32_t> op_chain, op_digest;
+    uint32_t checkpoints = 0;
+    for (uint32_t d : prog) {
+        checkpoints += d == MIRSHA_COMMIT_CHECKPOINT;
+        for (uint32_t node = 0; node < n_nodes_; node++) {
+            op_chain.push_back(node);
+            op_digest.push_back(d);
+        }
+    }
+    values_.assign((size_t)checkpoints * n_nodes_, {});
+    uint32_t k = 0;
+    int rc = mirsha_chains_commit(engine_.ctx(), chains_, table.data(), (uint32_t)(table.size() / 32), op_chain.data(),
+                                  op_digest.data(), (uint32_t)op_chain.size(),
+                                  values_.empty() ? nullptr : values_[0].data(), &k);
+    if (rc != MIRSHA_OK) panic(engine_.ctx(), rc, "could not commit");
+    if (k != values_.size()) throw std::runtime_error("checkpoint count mismatch");
+    std::vector<std::array<uint8_t, 32>> mine(checkpoints);
+    for (uint32_t j = 0; j < checkpoints; j++) mine[j] = values_[(size_t)j * n_nodes_ + node_];
+    return mine;
+}
+
+std::vector<CheckpointResult> Processor::CommitLoop(const Actions& actions) {
+    std::vector<CheckpointResult> out;
+    if (actions.Commits.empty()) return out;
+    if (!log_) throw std::runtime_error("actions.Commits without an application log");  // nil p.Log
+    const auto values = log_->CommitCycle(actions.Commits);
+    for (const Commit* c : actions.Commits)
+        if (c->Checkpoint) {  // processor.go:164-167, commit order
+            CheckpointResult r;
+            r.Checkpoint = c->Checkpoint;
+            r.Commit = c;
+            r.Value = values.at(out.size());
+            out.push_back(r);
+        }
+    return out;
+}
+
 ActionResults Processor::Process(const Actions& actions) {
     std::vector<std::array<uint8_t, 32>> digests;
     engine_.HashBatch(actions.Hash, digests, dedup_);  // one device call per Ready() cycle
-    return make_results(actions.Hash, digests);
+    ActionResults results = make_results(actions.Hash, digests);
+    results.Checkpoints = CommitLoop(actions);
+    return results;
 }
 
 PendingResults Processor::Submit(const Actions& actions) {
     PendingResults p;
+    // Applied here, ahead of the hashing (neither reads the other's results):
+    // cycles commit in submission order whatever the order of the Wait calls.
+    p.checkpoints_ = CommitLoop(actions);
     p.engine_ = &engine_;
     p.reqs_ = actions.Hash;
     p.digests_ = std::make_unique<std::vector<std::array<uint8_t, 32>>>();
@@ -130,6 +203,7 @@ PendingResults& PendingResults::operator=(PendingResults&& o) noexcept {
         ticket_ = o.ticket_;
         reqs_ = std::move(o.reqs_);
         digests_ = std::move(o.digests_);
+        checkpoints_ = std::move(o.checkpoints_);
         o.ticket_ = 0;
     }
     return *this;
@@ -146,7 +220,9 @@ ActionResults PendingResults::Wait() {
         engine_->Wait(ticket_);
         ticket_ = 0;
     }
-    return make_results(reqs_, *digests_);
+    ActionResults results = make_results(reqs_, *digests_);
+    results.Checkpoints = checkpoints_;
+    return results;
 }
 
 }  // namespace mirbft
@@ -191,6 +267,59 @@ extern "C" int mirbft_host_process_ex(int device, const uint8_t* const* data, co
             if (r.Digests[i].Request != &reqs[i]) throw std::runtime_error("origin order violated");
             memcpy(digests_out + 32ull * i, r.Digests[i].Digest.data(), 32);
         }
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && err_len) {
+            strncpy(err, e.what(), err_len - 1);
+            err[err_len - 1] = 0;
+        }
+        return -1;
+    }
+}
+
+extern "C" int mirbft_host_commit(int device, uint32_t n_nodes, const uint8_t* const* digest_ptr,
+                                  const uint32_t* batch_len, uint32_t n_commits, uint8_t* values_out,
+                                  uint32_t* n_checkpoints_out, int flags, char* err, uint32_t err_len) {
+    try {
+        mirbft::GpuEngine engine(device);
+        mirbft::DeviceLog log(engine, n_nodes);
+        mirbft::Processor p(engine, false, &log);
+        std::vector<mirbft::CommitBatch> batches(n_commits);
+        std::vector<mirbft::Checkpoint> cps(n_commits);
+        std::vector<mirbft::Commit> commits(n_commits);
+        mirbft::Actions a;
+        size_t at = 0;
+        for (uint32_t i = 0; i < n_commits; i++) {
+            if (batch_len[i] == UINT32_MAX) {
+                cps[i].SeqNo = i;
+                commits[i].Checkpoint = &cps[i];
+            } else {
+                for (uint32_t k = 0; k < batch_len[i]; k++, at++)
+                    batches[i].Digests.push_back(mirbft::Bytes{digest_ptr[at], digest_ptr[at] ? (size_t)32 : 0});
+                commits[i].Batch = &batches[i];
+            }
+            a.Commits.push_back(&commits[i]);
+        }
+        mirbft::ActionResults r;
+        if (flags & 2) {
+            mirbft::PendingResults pending = p.Submit(a);
+            r = pending.Wait();
+        } else {
+            r = p.Process(a);
+        }
+        size_t j = 0;
+        for (uint32_t i = 0; i < n_commits; i++)
+            if (commits[i].Checkpoint) {
+                if (j >= r.Checkpoints.size() || r.Checkpoints[j].Commit != &commits[i] ||
+                    r.Checkpoints[j].Checkpoint != &cps[i])
+                    throw std::runtime_error("commit order violated");
+                if (memcmp(r.Checkpoints[j].Value.data(), log.Values()[j * n_nodes].data(), 32) != 0)
+                    throw std::runtime_error("node 0's value differs from the log's");
+                j++;
+            }
+        if (j != r.Checkpoints.size()) throw std::runtime_error("checkpoint count mismatch");
+        for (size_t v = 0; v < log.Values().size(); v++) memcpy(values_out + 32 * v, log.Values()[v].data(), 32);
+        if (n_checkpoints_out) *n_checkpoints_out = (uint32_t)j;
         return 0;
     } catch (const std::exception& e) {
         if (err && err_len) {

@@ -8,6 +8,9 @@
 //   HashResult{Digest; Request}         actions.go:224-230   mirbft::HashResult
 //   ActionResults{Digests; ...}         actions.go:218-221   mirbft::ActionResults
 //   (*Processor).Process hash loop      processor.go:129-143 mirbft::Processor::Process
+//   Commit{Batch; Checkpoint}           actions.go:169-179   mirbft::Commit
+//   CheckpointResult{Checkpoint; Value} actions.go:234-243   mirbft::CheckpointResult
+//   (*Processor).Process commit loop    processor.go:145-168 mirbft::Processor (with a mirbft::DeviceLog)
 //
 // Processor::Process coalesces every HashRequest of one Ready() cycle into ONE
 // batched device call (mirsha_hash_slices) and returns Digests[i] for
@@ -17,6 +20,9 @@
 // mirsha_hash_slices_dedup) and the asynchronous Submit / Pending::Wait form
 // (mirsha_submit_slices / mirsha_wait) for overlapping the cycle's hashing
 // with its WAL writes and sends, as ProcessorWorkPool does (processor.go:447-470).
+// The commit loop: a cycle's actions.Commits go to the Processor's DeviceLog in
+// ONE mirsha_chains_commit call and ActionResults.Checkpoints holds one
+// CheckpointResult per checkpoint, in commit order; Commits without a log throw.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -27,6 +33,7 @@
 #include <vector>
 
 struct mirsha_ctx;
+struct mirsha_chains;
 
 namespace mirbft {
 
@@ -46,12 +53,40 @@ struct HashResult {
     const HashRequest* Request = nullptr;
 };
 
+// mirbft.Checkpoint (actions.go:192-205); opaque to the log.
+struct Checkpoint {
+    uint64_t SeqNo = 0;
+    const void* NetworkConfig = nullptr;
+    const void* ClientsState = nullptr;
+};
+
+// What the application log reads of a committed pb.QEntry: each request's
+// digest in order (recorder.go:222-223); size 0 = a null request.
+struct CommitBatch {
+    uint64_t SeqNo = 0;
+    std::vector<Bytes> Digests;
+};
+
+// mirbft.Commit (actions.go:169-179): a batch, or else a checkpoint.
+struct Commit {
+    const CommitBatch* Batch = nullptr;
+    const struct Checkpoint* Checkpoint = nullptr;
+};
+
+struct CheckpointResult {
+    const struct Checkpoint* Checkpoint = nullptr;  // the request that asked for it (actions.go:236)
+    const struct Commit* Commit = nullptr;
+    std::array<uint8_t, 32> Value{};
+};
+
 struct Actions {
     std::vector<const HashRequest*> Hash;  // actions.go:24
+    std::vector<const Commit*> Commits;    // actions.go:38
 };
 
 struct ActionResults {
-    std::vector<HashResult> Digests;  // actions.go:219
+    std::vector<HashResult> Digests;            // actions.go:219
+    std::vector<CheckpointResult> Checkpoints;  // actions.go:220
 };
 
 // Streaming hash.Hash (Write/Sum/Reset) for single-message callers.
@@ -90,6 +125,30 @@ private:
 // hash.Hash whose Sum runs on the GPU (buffers its writes).
 std::unique_ptr<Hash> NewGpuSha256(GpuEngine& engine);
 
+// The application log on the device: it stands where p.Log.Apply / p.Log.Snap
+// stand (processor.go:147,163), the testengine application's state
+// (NodeState.ActiveHash, recorder.go:186-256) in a mirsha_chains.  n_nodes = 1:
+// a node's own log (chain 0); n_nodes > 1: a testengine-style log, all nodes
+// commit the cycle's entries (the digest table is passed once).
+class DeviceLog {
+public:
+    explicit DeviceLog(GpuEngine& engine, uint32_t n_nodes = 1, uint32_t node = 0);
+    ~DeviceLog();
+    DeviceLog(const DeviceLog&) = delete;
+    DeviceLog& operator=(const DeviceLog&) = delete;
+    // One cycle's commits in ONE mirsha_chains_commit call; node `node`'s value
+    // per checkpoint, in commit order.  Values(): every node's, row
+    // checkpoint * n_nodes + node.
+    std::vector<std::array<uint8_t, 32>> CommitCycle(const std::vector<const Commit*>& commits);
+    const std::vector<std::array<uint8_t, 32>>& Values() const { return values_; }
+
+private:
+    GpuEngine& engine_;
+    mirsha_chains* chains_ = nullptr;
+    uint32_t n_nodes_, node_;
+    std::vector<std::array<uint8_t, 32>> values_;
+};
+
 // One submitted cycle; Wait() returns its ActionResults (origin order).
 // Owns the buffer the library writes the digests into (inside mirsha_wait, or
 // when a later submission retires this one's ring slot), so it is move-only
@@ -110,19 +169,23 @@ private:
     uint64_t ticket_ = 0;
     std::vector<const HashRequest*> reqs_;
     std::unique_ptr<std::vector<std::array<uint8_t, 32>>> digests_;
+    std::vector<CheckpointResult> checkpoints_;  // the commits were applied at Submit
 };
 
 class Processor {
 public:
-    explicit Processor(GpuEngine& engine, bool dedup = false) : engine_(engine), dedup_(dedup) {}
-    // processor.go:129-143, batched.
+    explicit Processor(GpuEngine& engine, bool dedup = false, DeviceLog* log = nullptr)
+        : engine_(engine), dedup_(dedup), log_(log) {}
+    // processor.go:129-143, batched; then the commit loop (:145-168) in one call.
     ActionResults Process(const Actions& actions);
     // Asynchronous Process: queue the cycle's hashing and return at once.
     PendingResults Submit(const Actions& actions);
 
 private:
+    std::vector<CheckpointResult> CommitLoop(const Actions& actions);
     GpuEngine& engine_;
     bool dedup_;
+    DeviceLog* log_;
 };
 
 }  // namespace mirbft
@@ -136,4 +199,13 @@ int mirbft_host_process(int device, const uint8_t* const* data, const uint64_t* 
 // asynchronous with a dropped (never waited) cycle before four more.
 int mirbft_host_process_ex(int device, const uint8_t* const* data, const uint64_t* len, uint32_t n,
                            uint8_t* digests_out, int flags, uint32_t* unique_out, char* err, uint32_t err_len);
+// One cycle's commits through mirbft::Processor with an n_nodes DeviceLog:
+// commit i is a batch of batch_len[i] requests whose digests are the next
+// batch_len[i] entries of digest_ptr (32 bytes each; NULL = a null request), or
+// a checkpoint if batch_len[i] == UINT32_MAX.  values_out: 32 bytes per
+// checkpoint and node (row checkpoint * n_nodes + node); flags bit 1 =
+// asynchronous (Submit, then Wait).
+int mirbft_host_commit(int device, uint32_t n_nodes, const uint8_t* const* digest_ptr, const uint32_t* batch_len,
+                       uint32_t n_commits, uint8_t* values_out, uint32_t* n_checkpoints_out, int flags, char* err,
+                       uint32_t err_len);
 }

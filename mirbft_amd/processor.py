@@ -8,6 +8,16 @@ HashResult{Digest, Request} actions.go:224-230     ``HashResult(digest, request)
 ActionResults{Digests, Checkpoints} :218-221       ``ActionResults``
 (*Processor).Process        processor.go:65-171    ``Processor.process`` (hash loop :129-143)
 ProcessorWorkPool.Process   processor.go:447-470   ``ProcessorWorkPool.process``
+Commit{Batch, Checkpoint}   actions.go:169-179     ``Commit(batch, checkpoint)``
+CheckpointResult            actions.go:234-243     ``CheckpointResult(checkpoint, value)``
+commit loop                 processor.go:145-168   ``Processor(log=DeviceLog(...))``
+
+The commit loop: a cycle's ``actions.commits`` (batches and checkpoints, in
+order) goes to the Processor's ``log`` in one call -- with a ``DeviceLog``
+one kernel launch over the device-resident checkpoint chains
+(``CheckpointChains.commit``) -- and ``ActionResults.checkpoints`` holds one
+``CheckpointResult`` per checkpoint, in commit order.  Commits without a log
+raise; a cycle without commits touches no log.
 
 ``Processor.process`` coalesces every HashRequest of one Ready() cycle into a
 single batched device call and returns ``Digests[i]`` for ``actions.hash[i]``
@@ -46,7 +56,10 @@ import threading
 from dataclasses import dataclass, field
 from typing import Any, Callable, Optional
 
-from .engine import Engine
+import numpy as np
+
+from ._lib import MIRSHA_COMMIT_CHECKPOINT, MIRSHA_NULL_INDEX
+from .engine import CheckpointChains, Engine
 
 
 @dataclass(eq=False)
@@ -65,16 +78,111 @@ class HashResult:
 
 
 @dataclass(eq=False)
+class Checkpoint:
+    """mirbft.Checkpoint (actions.go:192-205); opaque to the log but for seq_no."""
+
+    seq_no: int = 0
+    network_config: Any = None
+    clients_state: Any = None
+
+
+@dataclass(eq=False)
+class CommitBatch:
+    """What the application log reads of a committed pb.QEntry: the digest of
+    each request in order (recorder.go:222-223); ``None`` or ``b""`` is a null
+    request, whose Write changes nothing."""
+
+    digests: list = field(default_factory=list)
+    seq_no: int = 0
+
+
+@dataclass(eq=False)
+class Commit:
+    """mirbft.Commit (actions.go:169-179): a batch, or else a checkpoint."""
+
+    batch: Optional[CommitBatch] = None
+    checkpoint: Optional[Checkpoint] = None
+
+
+@dataclass(eq=False)
+class CheckpointResult:
+    """mirbft.CheckpointResult (actions.go:234-243): ``checkpoint`` is the
+    request of the Commit that asked for it, ``commit`` that Commit."""
+
+    checkpoint: Checkpoint
+    value: bytes
+    commit: Optional[Commit] = None
+
+
+@dataclass(eq=False)
 class Actions:
-    """Subset of mirbft.Actions (actions.go:18-52) the hash path reads."""
+    """Subset of mirbft.Actions (actions.go:18-52) the hash and commit paths read."""
 
     hash: list = field(default_factory=list)
+    commits: list = field(default_factory=list)
 
 
 @dataclass(eq=False)
 class ActionResults:
     digests: list = field(default_factory=list)
     checkpoints: list = field(default_factory=list)
+
+
+def commit_programme(commits, n_nodes: int = 1):
+    """Host-only: one cycle's ``actions.commits`` as the arguments of
+    ``CheckpointChains.commit`` for nodes 0..n_nodes-1, which all commit the
+    same entries (testengine: NodeState.Commit on every node,
+    recorder.go:213-256).  Returns (table, op_chain, op_digest): the (m, 32)
+    table holds each non-null request digest ONCE, in commit order, whatever
+    the number of nodes; each step of the cycle is n_nodes consecutive ops
+    (node 0 first), so value row ``j * n_nodes + node`` is checkpoint j's value
+    on that node."""
+    rows, prog = [], []
+    for k, commit in enumerate(commits):
+        if (commit.batch is None) == (commit.checkpoint is None):
+            raise ValueError(f"commits[{k}]: exactly one of batch and checkpoint must be set")
+        if commit.checkpoint is not None:
+            prog.append(MIRSHA_COMMIT_CHECKPOINT)
+            continue
+        for d in commit.batch.digests:
+            if d is None or len(d) == 0:
+                prog.append(MIRSHA_NULL_INDEX)
+                continue
+            if len(d) != 32:
+                raise ValueError(f"commits[{k}]: a request digest of {len(d)} bytes")
+            prog.append(len(rows))
+            rows.append(bytes(d))
+    table = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), 32)
+    op_digest = np.repeat(np.asarray(prog, dtype=np.uint32), n_nodes)
+    op_chain = np.tile(np.arange(n_nodes, dtype=np.uint32), len(prog))
+    return table, op_chain, op_digest
+
+
+class DeviceLog:
+    """The application log of a Processor on the device: it stands where
+    ``p.Log.Apply`` and ``p.Log.Snap`` stand in the commit loop
+    (processor.go:147,163), with the testengine application's state
+    (NodeState.ActiveHash, recorder.go:186-256) held in a ``CheckpointChains``.
+    One cycle's ``actions.commits`` is ONE ``CheckpointChains.commit`` call.
+    ``n_nodes = 1`` is a node's own log (chain 0); a testengine-style log
+    drives the chains of n_nodes nodes, which commit the same entries, from the
+    one cycle.  ``values`` keeps the last cycle's (checkpoints, n_nodes, 32)
+    array; ``commit_cycle`` returns node ``node``'s."""
+
+    def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, chains=None):
+        if not 0 <= node < n_nodes:
+            raise ValueError(f"node {node} of {n_nodes}")
+        self.n_nodes, self.node = int(n_nodes), int(node)
+        self.chains = chains if chains is not None else CheckpointChains(engine, self.n_nodes)
+        self.values = np.empty((0, self.n_nodes, 32), dtype=np.uint8)
+
+    def commit_cycle(self, commits) -> list:
+        table, op_chain, op_digest = commit_programme(commits, self.n_nodes)
+        self.values = self.chains.commit(table, op_chain, op_digest).reshape(-1, self.n_nodes, 32)
+        return [v.tobytes() for v in self.values[:, self.node]]
+
+    def close(self) -> None:
+        self.chains.close()
 
 
 class GpuHash:
@@ -113,11 +221,14 @@ def _results(reqs, digests) -> ActionResults:
 class PendingResults:
     """Hash results of one submitted cycle; ``wait()`` returns its ActionResults."""
 
-    def __init__(self, engine: Engine, reqs, ticket, parts=None):
+    def __init__(self, engine: Engine, reqs, ticket, parts=None, checkpoints=None):
         """``ticket``: the cycle's one submission, or None; ``parts`` instead:
-        [(ticket, request indices)] of a cycle split over several submissions."""
+        [(ticket, request indices)] of a cycle split over several submissions.
+        ``checkpoints``: the cycle's CheckpointResults (its commits were applied
+        when it was submitted, so cycles commit in submission order)."""
         self._engine, self._reqs, self._ticket = engine, reqs, ticket
         self._parts = parts
+        self._checkpoints = checkpoints if checkpoints is not None else []
         self._results: Optional[ActionResults] = None
 
     def _tickets(self):
@@ -154,7 +265,8 @@ class PendingResults:
                 self._part(ticket, idx, digests)
             # Digests[i] for actions.Hash[i] (processor.go:139)
             self._results = ActionResults(digests=[HashResult(digest=digests[i], request=r)
-                                                   for i, r in enumerate(reqs)])
+                                                   for i, r in enumerate(reqs)],
+                                          checkpoints=self._checkpoints)
         return self._results
 
 
@@ -162,13 +274,36 @@ class Processor:
     """Hash stage of mirbft.Processor; batches one Ready() cycle per device call."""
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, dedup: bool = False,
-                 verify_on_device: bool = False):
+                 verify_on_device: bool = False, log=None):
+        """``log``: the application log (p.Log, processor.go:147,163), e.g. a
+        ``DeviceLog``: any object whose ``commit_cycle(commits)`` applies one
+        cycle's commits and returns one value per checkpoint among them."""
         self.engine = engine if engine is not None else Engine(device)
         self.dedup = dedup
         self.verify_on_device = verify_on_device
+        self.log = log
 
     def process(self, actions: Actions) -> ActionResults:
-        reqs = actions.hash
+        results = self._process_hash(actions.hash)  # the hash loop, then the commit loop
+        results.checkpoints = self._commit(actions)
+        return results
+
+    def _commit(self, actions) -> list:
+        """The commit loop (processor.go:145-168): the cycle's commits go to the
+        log in one call; Checkpoints in commit order, each pointing back at
+        its Commit.  No commits: nothing is called."""
+        commits = list(getattr(actions, "commits", None) or [])
+        if not commits:
+            return []
+        if self.log is None:  # the reference dereferences a nil p.Log
+            raise RuntimeError("actions.commits without an application log (Processor(log=...))")
+        asked = [c for c in commits if c.checkpoint is not None]
+        values = self.log.commit_cycle(commits)
+        if len(values) != len(asked):
+            raise RuntimeError(f"the log returned {len(values)} values for {len(asked)} checkpoints")
+        return [CheckpointResult(checkpoint=c.checkpoint, value=bytes(v), commit=c) for c, v in zip(asked, values)]
+
+    def _process_hash(self, reqs) -> ActionResults:
         if not reqs:
             return ActionResults(digests=[])
         if self.verify_on_device:
@@ -201,14 +336,18 @@ class Processor:
         carry an expectation are one such submission and the rest one
         ``submit_slices(dedup=True)`` (the two do not combine in one)."""
         reqs = list(actions.hash)
+        # The commits are applied here, synchronously and ahead of the hashing
+        # (neither reads the other's results), so that cycles commit in
+        # submission order whatever the order of the wait() calls.
+        cps = self._commit(actions)
         if not reqs:
-            return PendingResults(self.engine, reqs, None)
+            return PendingResults(self.engine, reqs, None, checkpoints=cps)
         if not self.verify_on_device:
             return PendingResults(self.engine, reqs, self.engine.submit_slices([r.data for r in reqs],
-                                                                               dedup=self.dedup))
+                                                                               dedup=self.dedup), checkpoints=cps)
         if not self.dedup:
             return PendingResults(self.engine, reqs, self.engine.submit_slices_expect(
-                [r.data for r in reqs], [r.expected for r in reqs]))
+                [r.data for r in reqs], [r.expected for r in reqs]), checkpoints=cps)
         check = [i for i, r in enumerate(reqs) if r.expected is not None]
         plain = [i for i, r in enumerate(reqs) if r.expected is None]
         parts = []
@@ -217,7 +356,7 @@ class Processor:
                                                            [reqs[i].expected for i in check]), check))
         if plain:
             parts.append((self.engine.submit_slices([reqs[i].data for i in plain], dedup=True), plain))
-        return PendingResults(self.engine, reqs, None, parts)
+        return PendingResults(self.engine, reqs, None, parts, checkpoints=cps)
 
 
 class ProcessorWorkPool(Processor):
@@ -228,8 +367,8 @@ class ProcessorWorkPool(Processor):
     """
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, hash_workers: int = 0,
-                 transmit_workers: int = 0, dedup: bool = False, verify_on_device: bool = False):
-        super().__init__(engine, device, dedup, verify_on_device)
+                 transmit_workers: int = 0, dedup: bool = False, verify_on_device: bool = False, log=None):
+        super().__init__(engine, device, dedup, verify_on_device, log)
         self._mutex = threading.Lock()
         self.hash_workers = hash_workers
 
