@@ -569,6 +569,85 @@ int mirsha_chains_commit_device(mirsha_ctx* ctx, mirsha_chains* chains, const ui
                                 const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                 uint8_t* values_out, uint32_t* n_values_out);
 
+/* ------------------------------ a cycle's Commits on the asynchronous ring */
+/* ProcessorWorkPool.Process starts commitInParallel beside hashInParallel and
+ * collects both at the end (processor.go:447-470, :363-394).  The ring form
+ * of mirsha_chains_commit does the same: the programme is queued, the call
+ * returns, and the values are complete when the ticket retires.
+ *
+ * After a checkpoint a chain restarts from Hasher(), so the stretches of one
+ * chain between checkpoints are independent hashes.  The ring form cuts each
+ * active chain's entries after every checkpoint entry into SEGMENTS and runs
+ * one lane per segment: a cycle's commit costs its longest stretch, not their
+ * sum. */
+#define MIRSHA_COMMIT_SEG_FIRST 1u /* the chain's first segment: starts from the stored state */
+#define MIRSHA_COMMIT_SEG_LAST 2u  /* holds the chain's final entry: stores the state it ends in */
+
+/* Host-only, like mirsha_commit_plan, whose output it is built on (same
+ * checks, codes and *bad_op_out; ent_out, *n_active_out, *n_entries_out and
+ * *n_values_out are that plan's, unchanged).  Segment s, s < *n_seg_out:
+ *   seg_chain_out[s]: its chain;
+ *   entries ent_out[sfirst_out[s] .. sfirst_out[s+1]), sfirst_out[0] = 0,
+ *     sfirst_out[n_seg] = *n_entries_out;
+ *   seg_flags_out[s]: MIRSHA_COMMIT_SEG_FIRST starts from the chain's stored
+ *     midstate, pending digest and count; every other segment starts from H0
+ *     with nothing pending and count 0.  MIRSHA_COMMIT_SEG_LAST stores the
+ *     state it ends in as the chain's.
+ * A segment ends with a checkpoint entry or with the chain's final entry: a
+ * chain whose entries end with a checkpoint gets no empty segment behind it
+ * (its last segment leaves Hasher()).  Segments are chain-major (chains
+ * ascending), in op order within a chain.  *n_seg_out = active chains +
+ * checkpoint entries that are not their chain's final entry.
+ * Capacities: seg_chain_out and seg_flags_out n_ops entries, sfirst_out one
+ * more, ent_out n_ops. */
+int mirsha_commit_seg_plan(const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint32_t n_chains,
+                           uint32_t n_digests, uint32_t* seg_chain_out, uint32_t* sfirst_out, uint32_t* seg_flags_out,
+                           uint32_t* ent_out, uint32_t* n_seg_out, uint32_t* n_active_out, uint32_t* n_entries_out,
+                           uint32_t* n_values_out, uint32_t* bad_op_out);
+
+/* mirsha_chains_commit as a ring submission: arguments, checks, error codes
+ * and messages are that call's.  Before the call returns every check has run
+ * on the host, *n_values_out is written, and op_chain, op_digest and the
+ * (host) digest table are copied into the ring slot's page-locked block: the
+ * caller may reuse them at once.  The call takes the context's next ticket and
+ * ring slot like mirsha_submit_*; the ticket is retired by mirsha_wait /
+ * mirsha_poll in ticket order, mixed freely with hashing tickets, and a fifth
+ * submission retires the oldest.  values_out (32 bytes per checkpoint op, op
+ * order) must stay valid until the ticket retires and is complete then.  A
+ * validation failure queues nothing, consumes no ticket and leaves every state
+ * untouched.  n_ops == 0 or null writes only: a valid ticket, nothing
+ * launched.
+ *
+ * The device work runs on a stream of the context's own for commits (created
+ * at the first such call), so the one latency-bound commit wave does not queue
+ * behind the hashing kernels on the context's stream, nor they behind it (their
+ * device time beside it: DESIGN.md 1.4.1, measurement c): one H2D
+ * copy of the slot's block, one launch of the segment kernel (timing id 1),
+ * the slot's completion event.  When a chain's first and last segment fall
+ * into different waves, a device-to-device copy of the states precedes the
+ * launch (the first segments read that copy; without it a last segment's store
+ * could overtake the first segment's load).  The kernel stores the values
+ * straight into a page-locked, 16-byte aligned values_out, otherwise into
+ * page-locked rows of the slot that are copied out at retirement: there is no
+ * D2H copy.  Commit submissions run in submission order.  The synchronous
+ * mirsha_chains_absorb / _sum / _reset / _commit on an object with a commit in
+ * flight first make the context's stream wait for it, so both forms mix on
+ * one object without the caller waiting; mirsha_chains_destroy waits for the
+ * object's last queued commit.  mirsha_ctx_host_profile of a retired commit
+ * ticket: validate = checks and plan, pack = the staging copy, device = queued
+ * -> complete, scatter = the values' copy. */
+int mirsha_chains_commit_submit(mirsha_ctx* ctx, mirsha_chains* chains, const uint8_t* digests, uint32_t n_digests,
+                                const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
+                                uint8_t* values_out, uint32_t* n_values_out, uint64_t* ticket_out);
+/* The same with the table in device memory (16-byte aligned).  The commit
+ * stream waits on an event recorded on the context's stream at submission, so
+ * the table is read behind whatever was queued there (e.g. the hashing that
+ * writes it); it must stay intact until the ticket retires. */
+int mirsha_chains_commit_submit_device(mirsha_ctx* ctx, mirsha_chains* chains, const uint8_t* d_digests,
+                                       uint32_t n_digests, const uint32_t* op_chain, const uint32_t* op_digest,
+                                       uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
+                                       uint64_t* ticket_out);
+
 /* ------------------------------------------------- multi-GPU (one process) */
 /* Shards the n requests by contiguous range across ndev devices (balanced by
  * block count), one context per device, host gather into origin order.  No

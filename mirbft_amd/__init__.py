@@ -7,8 +7,8 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 """
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
-from .engine import (CheckpointChains, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order,
-                     commit_plan, dedup_plan, device_count, expect_bitmap, expect_plan, hash_batch_multi,
+from .engine import (CheckpointChains, CommitTicket, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order,
+                     commit_plan, commit_seg_plan, dedup_plan, device_count, expect_bitmap, expect_plan, hash_batch_multi,
                      mismatch_indices)
 from .processor import (ActionResults, Actions, Checkpoint, CheckpointResult, Commit, CommitBatch, DeviceLog, GpuHash,
                         HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, commit_programme,
@@ -20,10 +20,12 @@ __all__ = [
     "SliceArrays",
     "Ticket",
     "ExpectTicket",
+    "CommitTicket",
     "dedup_plan",
     "expect_plan",
     "expect_bitmap",
     "commit_plan",
+    "commit_seg_plan",
     "commit_programme",
     "Checkpoint",
     "CheckpointResult",

@@ -23,6 +23,8 @@ MIRSHA_ENODEV = -5
 MIRSHA_NULL_INDEX = 0xFFFFFFFF
 MIRSHA_COMMIT_CHECKPOINT = 0xFFFFFFFE
 MIRSHA_COMMIT_ENTRY_CHECKPOINT = 0x80000000
+MIRSHA_COMMIT_SEG_FIRST = 1
+MIRSHA_COMMIT_SEG_LAST = 2
 MIRSHA_MAX_MESSAGE_BYTES = 0xFFFFFF00
 MIRSHA_MAX_DEVICE_ARENA_BYTES = 0xFFFFFF00
 MIRSHA_SUBMIT_DEDUP = 1
@@ -142,6 +144,19 @@ SIGNATURES = {
     "mirsha_chains_commit_device": (
         c_int,
         [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, _u32p],
+    ),
+    "mirsha_commit_seg_plan": (
+        c_int,
+        [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, _u32p, _u32p, _u32p,
+         _u32p, _u32p],
+    ),
+    "mirsha_chains_commit_submit": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, _u32p, _u64p],
+    ),
+    "mirsha_chains_commit_submit_device": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, _u32p, _u64p],
     ),
     "mirsha_hash_batch_multi": (
         c_int,

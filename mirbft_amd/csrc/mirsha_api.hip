@@ -144,6 +144,7 @@ void mirsha_ctx_destroy(mirsha_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->xin) (void)hipStreamSynchronize(c->xin);
     if (c->xout) (void)hipStreamSynchronize(c->xout);
+    if (c->xcommit) (void)hipStreamSynchronize(c->xcommit);
     for (auto& t : c->timers) {
         for (auto& pr : t.pending) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
         for (auto e : t.pool) (void)hipEventDestroy(e);
@@ -162,9 +163,11 @@ void mirsha_ctx_destroy(mirsha_ctx* c) {
     for (auto e : c->xev) (void)hipEventDestroy(e);
     if (c->xin) (void)hipStreamDestroy(c->xin);
     if (c->xout) (void)hipStreamDestroy(c->xout);
+    if (c->xcommit) (void)hipStreamDestroy(c->xcommit);
     for (auto& sl : c->slots) {
         sl.stage.release(); sl.dig.release(); sl.dev.release(); sl.stage2.release(); sl.dev2.release();
         sl.xp.stage.release(); sl.xp.verdict.release(); sl.xp.dev.release();
+        sl.cm.stage.release(); sl.cm.dev.release(); sl.cm.snap.release(); sl.cm.rows.release();
         if (sl.done) (void)hipEventDestroy(sl.done);
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
         if (sl.ev_kern) (void)hipEventDestroy(sl.ev_kern);
@@ -352,6 +355,10 @@ int mirsha_chains_create(mirsha_ctx* c, uint32_t n, mirsha_chains** out) {
 void mirsha_chains_destroy(mirsha_chains* ch) {
     if (!ch) return;
     (void)hipSetDevice(ch->device);
+    if (ch->ev_commit) {  // the last queued commit submission still uses the state
+        (void)hipEventSynchronize(ch->ev_commit);
+        (void)hipEventDestroy(ch->ev_commit);
+    }
     for (DevBuf* b : {&ch->d_h, &ch->d_pend, &ch->d_cnt, &ch->d_dig, &ch->d_pos, &ch->d_act, &ch->d_afirst,
                       &ch->d_which, &ch->d_out, &ch->d_plan})
         b->release();
@@ -380,6 +387,7 @@ int mirsha_chains_absorb(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
     std::vector<uint32_t> pos(m);
     for (uint32_t i = 0; i < m; i++) pos[count[chain_of[i]]++] = i;
     if (int rc = use_device(c)) return rc;
+    if (int rc = chains_order(c, ch)) return rc;
     const uint32_t na = (uint32_t)act.size();
     HIP_TRY(c, ch->d_dig.ensure(32ull * m));
     HIP_TRY(c, ch->d_pos.ensure(4ull * m));
@@ -407,6 +415,7 @@ int chains_which(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32
     for (uint32_t j = 0; j < k; j++)
         if (which[j] >= ch->n) return fail(c, MIRSHA_EINVAL, "which[%u] = %u >= %u", j, which[j], ch->n);
     if (int rc = use_device(c)) return rc;
+    if (int rc = chains_order(c, ch)) return rc;
     HIP_TRY(c, ch->d_which.ensure(4ull * k));
     HIP_TRY(c, hipMemcpyAsync(ch->d_which.p, which, 4ull * k, hipMemcpyHostToDevice, c->stream));
     return MIRSHA_OK;
@@ -477,6 +486,7 @@ static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
     if (values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u checkpoints)", values);
     if (na == 0) return MIRSHA_OK;  // null writes only
     if (int r = use_device(c)) return r;
+    if (int r = chains_order(c, ch)) return r;
     const uint8_t* d_dig = digests;
     if (!on_device && n_digests) {
         HIP_TRY(c, ch->d_dig.ensure(32ull * n_digests));

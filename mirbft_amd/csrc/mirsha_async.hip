@@ -156,7 +156,10 @@ int async_complete(mirsha_ctx* c, AsyncSlot& sl) {
     const auto t_done = Clock::now();
     sl.prof[MIRSHA_PROF_DEVICE] = std::chrono::duration<double, std::milli>(t_done - sl.t_queued).count();
     const uint8_t* d = sl.dig.as<uint8_t>();
-    if (sl.xp.on && sl.xp.select) {
+    if (sl.cm.on) {
+        // commit submission: the values, unless the kernel stored them into values_out itself
+        if (!sl.cm.rows_direct && sl.cm.n_values) memcpy(sl.cm.user_values, sl.cm.rows.p, 32ull * sl.cm.n_values);
+    } else if (sl.xp.on && sl.xp.select) {
         // mixed submission: only the kept rows are copied (expect_complete)
     } else if (sl.direct) {
         // mirsha_submit_batch into page-locked digests_out: already there
@@ -219,6 +222,7 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     sl.rank.clear();
     sl.direct = false;
     sl.xp.on = sl.xp.select = false;
+    sl.cm.on = false;
     HIP_TRY(c, sl.dig.ensure(32ull * std::max<uint32_t>(n, 1)));
     if (!sl.done) HIP_TRY(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     // Mixed submission with expectations: the select kernel stands where the
@@ -491,6 +495,7 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     t0 = Clock::now();
     sl.rank.clear();
     sl.xp.on = sl.xp.select = false;
+    sl.cm.on = false;
     for (hipEvent_t* e : {&sl.done, &sl.ev_in, &sl.ev_kern})
         if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
     // Request bytes in on xin, the kernel on the context stream; digests

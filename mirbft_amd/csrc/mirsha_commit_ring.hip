@@ -1,0 +1,385 @@
+// mirsha_commit_ring.hip — a cycle's Commits on the asynchronous ring
+// (mirsha_chains_commit_submit / _submit_device, include/mirsha.h): the
+// commit stage of ProcessorWorkPool (commitInParallel, processor.go:363-394,
+// :447-470) beside its hash stage (mirsha_async.hip).  A translation unit of
+// its own, as mirsha_expect.hip: the hashing kernels' sources and code object
+// are untouched, and the synchronous mirsha_chains_commit keeps its kernel.
+#include <hip/hip_ext.h>
+
+#include "mirsha_ctx.h"
+
+namespace mirsha {
+
+namespace {
+
+// One step of a lane's programme; the step structure is chains_commit_kernel's
+// (mirsha_kernels.hip): at most one compression, i.e. two whole digests (the
+// first may be the pending one), or a checkpoint's single final block, or a
+// lone last write that becomes the pending digest without a compression.
+// Restated here, not shared: that file is no header, and neither its text nor
+// its code object may change (bench.py's traffic_key hashes it).
+struct SegStep {
+    uint4 a0, a1, b0, b1;  // raw rows of the two halves (zeros where the step loads none)
+    uint64_t bits;         // checkpoint: the message's bit length
+    uint32_t row;          // checkpoint: output row
+    bool use_pend;         // first half = the pending digest
+    bool have_a;           // checkpoint: a first half precedes the 0x80
+    bool write, cp;        // compress two digests / the final block (neither: nothing to hash)
+    bool keep;             // a lone last write: the first half becomes the pending digest
+};
+
+// Plans the step of a lane at entry e (x0 = ent[e], xn = ent[e + 1], each
+// loaded only below `end`), requests its digest rows, moves e and the digest
+// count n past it and loads the entries of the step after it.  Which entries
+// a step consumes depends on the entry kinds and the parity only, never on a
+// hash value, so this walk runs one step ahead of the hashing.  Every load is
+// guarded by the lane's own sfirst range: past `end` lie the next segment's
+// entries or the end of the array.
+__device__ __forceinline__ SegStep seg_fetch(const uint8_t* __restrict__ digests, const uint32_t* __restrict__ ent,
+                                             uint32_t end, uint32_t& e, uint64_t& n, uint32_t& x0, uint32_t& xn) {
+    SegStep s;
+    const bool live = e < end;
+    const bool odd = (n & 1u) != 0u;
+    const bool take0 = live && !odd && !(x0 & kCommitEntryCheckpoint);  // first half from the table
+    const uint32_t e1 = e + (take0 ? 1u : 0u);
+    const bool live1 = live && e1 < end;  // odd && live: e1 == e, so live1
+    const uint32_t x1 = take0 ? xn : x0;
+    s.write = live1 && !(x1 & kCommitEntryCheckpoint);
+    s.cp = live1 && (x1 & kCommitEntryCheckpoint) != 0u;
+    s.use_pend = odd && live1;
+    s.have_a = odd || take0;
+    s.keep = take0 && !live1;
+    s.row = x1 & ~kCommitEntryCheckpoint;
+    s.bits = (n + (take0 ? 1u : 0u)) * 256u;
+    s.a0 = s.a1 = s.b0 = s.b1 = make_uint4(0u, 0u, 0u, 0u);
+    if (take0) {
+        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x0);
+        s.a0 = d[0];
+        s.a1 = d[1];
+    }
+    if (s.write) {
+        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x1);
+        s.b0 = d[0];
+        s.b1 = d[1];
+    }
+    n = s.cp ? 0u : n + (take0 ? 1u : 0u) + (s.write ? 1u : 0u);
+    e = e1 + (live1 ? 1u : 0u);
+    x0 = e < end ? ent[e] : 0u;
+    xn = e + 1u < end ? ent[e + 1u] : 0u;  // e <= end <= 2^31: no wrap
+    return s;
+}
+
+__device__ __forceinline__ void seg_be_words(const uint4& v, uint32_t w[4]) {
+    w[0] = __builtin_bswap32(v.x); w[1] = __builtin_bswap32(v.y);
+    w[2] = __builtin_bswap32(v.z); w[3] = __builtin_bswap32(v.w);
+}
+
+// The wave's issue priority, once at entry.  The priority is wave-uniform;
+// readfirstlane keeps the branches scalar, so exactly one s_setprio executes
+// (s_setprio ignores exec: fixed_prio, mirsha_kernels.hip).
+__device__ __forceinline__ void seg_prio(uint32_t p) {
+    p = (uint32_t)__builtin_amdgcn_readfirstlane((int)p);
+    if (p >= 3u) __builtin_amdgcn_s_setprio(3);
+    else if (p == 2u) __builtin_amdgcn_s_setprio(2);
+    else if (p == 1u) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+}
+
+}  // namespace
+
+// One lane per segment of the cycle's commit programme
+// (mirsha_commit_seg_plan): segment s runs entries ent[sfirst[s] ..
+// sfirst[s+1]) of chain seg_chain[s].  What differs from chains_commit_kernel:
+// a lane that is not its chain's FIRST segment loads no state (it starts from
+// Hasher()), one that is not the LAST stores none, the checkpoint rows are
+// plain 128-bit vector stores (`out` may be host-visible page-locked memory),
+// and the wave raises its issue priority once at entry: it is one
+// latency-bound wave meant to run beside a saturating request launch whose
+// waves run at priorities up to 3.  No atomics, no waiting; the only
+// cross-lane dependence is the ballot that keeps the loop wave-uniform.
+//
+// FIRST lanes read h_in / pend_in / cnt_in, LAST lanes write h / pend / cnt.
+// The two are the same arrays unless a chain's FIRST and LAST segment lie in
+// different waves: a LAST lane's store could then overtake the FIRST lane's
+// load, and the host passes a copy of the states taken ahead of the launch.
+__global__ __launch_bounds__(kBlockThreads) void chains_commit_seg_kernel(
+    const uint8_t* __restrict__ digests, const uint32_t* __restrict__ ent, const uint32_t* __restrict__ seg_chain,
+    const uint32_t* __restrict__ sfirst, const uint32_t* __restrict__ seg_flags, uint32_t n_seg, const uint32_t* h_in,
+    const uint32_t* pend_in, const uint64_t* cnt_in, uint32_t* h, uint32_t* pend, uint64_t* cnt, uint4* out,
+    uint32_t prio) {
+    seg_prio(prio);
+    const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
+    const bool valid = k < n_seg;
+    const uint32_t c = valid ? seg_chain[k] : 0u;
+    const uint32_t flags = valid ? seg_flags[k] : 0u;
+    uint32_t e = valid ? sfirst[k] : 0u;
+    const uint32_t end = valid ? sfirst[k + 1] : 0u;
+    uint32_t st[8], pw[8];
+    uint64_t n = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        st[i] = kH0[i];
+        pw[i] = 0u;
+    }
+    if (flags & MIRSHA_COMMIT_SEG_FIRST) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            st[i] = h_in[8ull * c + i];
+            pw[i] = pend_in[8ull * c + i];
+        }
+        n = cnt_in[c];
+    }
+    uint32_t x0 = e < end ? ent[e] : 0u;
+    uint32_t xn = e + 1u < end ? ent[e + 1u] : 0u;
+    SegStep s = seg_fetch(digests, ent, end, e, n, x0, xn);
+    // Wave-uniform: a lane whose step does nothing has reached its end (only a
+    // programme's last step can be without a compression).
+    while (__ballot(s.write || s.cp || s.keep) != 0ull) {
+        const SegStep nx = seg_fetch(digests, ent, end, e, n, x0, xn);
+        uint32_t w[16];
+        seg_be_words(s.a0, w); seg_be_words(s.a1, w + 4); seg_be_words(s.b0, w + 8); seg_be_words(s.b1, w + 12);
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            if (s.use_pend) w[i] = pw[i];
+            if (s.keep) pw[i] = w[i];
+        }
+        if (s.cp) {
+            if (s.have_a) w[8] = 0x80000000u; else w[0] = 0x80000000u;
+            w[14] = (uint32_t)(s.bits >> 32);
+            w[15] = (uint32_t)s.bits;
+        }
+        if (s.write || s.cp) compress_asm_lat(st, w);
+        if (s.cp) {
+            uint4* o = out + 2ull * s.row;
+            o[0] = make_uint4(__builtin_bswap32(st[0]), __builtin_bswap32(st[1]), __builtin_bswap32(st[2]),
+                              __builtin_bswap32(st[3]));
+            o[1] = make_uint4(__builtin_bswap32(st[4]), __builtin_bswap32(st[5]), __builtin_bswap32(st[6]),
+                              __builtin_bswap32(st[7]));
+#pragma unroll
+            for (int i = 0; i < 8; i++) st[i] = kH0[i];
+        }
+        s = nx;
+    }
+    if (flags & MIRSHA_COMMIT_SEG_LAST) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            h[8ull * c + i] = st[i];
+            pend[8ull * c + i] = pw[i];
+        }
+        cnt[c] = n;
+    }
+}
+
+// Launched as every kernel of the library is (launch_k, mirsha_kernels.hip):
+// with the thread's pending timing events bound to the dispatch when a timed
+// launch set them.
+hipError_t launch_chains_commit_seg(const uint8_t* digests, const uint32_t* ent, const uint32_t* seg_chain,
+                                    const uint32_t* sfirst, const uint32_t* seg_flags, uint32_t n_seg,
+                                    const uint32_t* h_in, const uint32_t* pend_in, const uint64_t* cnt_in, uint32_t* h,
+                                    uint32_t* pend, uint64_t* cnt, uint8_t* out, uint32_t prio, hipStream_t s) {
+    if (n_seg == 0) return hipSuccess;
+    const uint32_t grid = (n_seg + kBlockThreads - 1u) / kBlockThreads;
+    uint4* o = reinterpret_cast<uint4*>(out);
+    LaunchEvents& ev = next_launch_events();
+    if (ev.start && ev.stop) {
+        const hipEvent_t e0 = ev.start, e1 = ev.stop;
+        ev = LaunchEvents{};
+        hipExtLaunchKernelGGL(chains_commit_seg_kernel, dim3(grid), dim3(kBlockThreads), 0, s, e0, e1, 0u, digests, ent,
+                              seg_chain, sfirst, seg_flags, n_seg, h_in, pend_in, cnt_in, h, pend, cnt, o, prio);
+    } else {
+        chains_commit_seg_kernel<<<grid, kBlockThreads, 0, s>>>(digests, ent, seg_chain, sfirst, seg_flags, n_seg, h_in,
+                                                                pend_in, cnt_in, h, pend, cnt, o, prio);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace mirsha
+
+namespace mirsha_api {
+
+namespace {
+
+// The issue priority of the segment kernel's waves.  MIRSHA_AB=1
+// MIRSHA_COMMIT_PRIO=n (0-3) is the A/B knob.
+constexpr uint32_t kCommitSegPrio = 3;
+uint32_t commit_seg_prio() {
+    const char* e = mirsha::ab_getenv("MIRSHA_COMMIT_PRIO");
+    if (e && e[0] >= '0' && e[0] <= '3' && e[1] == 0) return (uint32_t)(e[0] - '0');
+    return kCommitSegPrio;
+}
+
+// Both forms of mirsha_chains_commit_submit.  Order: every check and the plan
+// (into the context's scratch; a failure leaves the ring as it was), then the
+// slot (retiring its previous ticket), the staging copy, and the device work
+// on the commit stream.
+int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
+                  const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
+                  uint32_t* n_values_out, uint64_t* ticket_out) {
+    if (!c || !ch || !n_values_out || !ticket_out) return MIRSHA_EINVAL;
+    *n_values_out = 0;
+    auto t0 = Clock::now();
+    double ph[MIRSHA_PROF_PHASES] = {};
+    uint32_t ns = 0, na = 0, entries = 0, values = 0;
+    const size_t o_pfirst = n_ops, o_pflags = 2ull * n_ops + 1u, o_pent = 3ull * n_ops + 1u;  // in c->cm_plan
+    if (n_ops) {
+        if (!op_chain || !op_digest) return fail(c, MIRSHA_EINVAL, "NULL argument");
+        if (n_digests && !digests) return fail(c, MIRSHA_EINVAL, "NULL digest table (%u digests)", n_digests);
+        if (on_device && (reinterpret_cast<uintptr_t>(digests) & 15u))
+            return fail(c, MIRSHA_EINVAL, "d_digests must be 16-byte aligned");
+        if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
+        if (n_ops > MIRSHA_COMMIT_ENTRY_CHECKPOINT || n_digests > MIRSHA_COMMIT_ENTRY_CHECKPOINT)
+            return fail(c, MIRSHA_ERANGE, "%u ops / %u digests > %u", n_ops, n_digests, MIRSHA_COMMIT_ENTRY_CHECKPOINT);
+        if (c->cm_plan.size() < o_pent + n_ops) c->cm_plan.resize(o_pent + n_ops);
+        uint32_t* plan = c->cm_plan.data();
+        uint32_t bad = UINT32_MAX;
+        const int rc = mirsha_commit_seg_plan(op_chain, op_digest, n_ops, ch->n, n_digests, plan, plan + o_pfirst,
+                                              plan + o_pflags, plan + o_pent, &ns, &na, &entries, &values, &bad);
+        if (rc != MIRSHA_OK) {
+            if (bad == UINT32_MAX) return fail(c, rc, "commit plan failed");
+            if (op_chain[bad] >= ch->n) return fail(c, rc, "op_chain[%u] = %u >= %u", bad, op_chain[bad], ch->n);
+            return fail(c, rc, "op_digest[%u] = %u >= %u", bad, op_digest[bad], n_digests);
+        }
+        if (values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u checkpoints)", values);
+    }
+    ph[MIRSHA_PROF_VALIDATE] = ms_since(t0);
+    t0 = Clock::now();
+    if (int rc = use_device(c)) return rc;
+    AsyncSlot& sl = c->slots[(c->next_ticket - 1) % kAsyncSlots];
+    if (sl.busy)
+        if (int rc = async_wait_upto(c, sl.ticket)) return rc;  // ring full: retire the oldest
+    CommitSlot& cm = sl.cm;
+    if (!sl.done) HIP_TRY(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    if (ns) {
+        if (!c->xcommit) HIP_TRY(c, hipStreamCreateWithFlags(&c->xcommit, hipStreamNonBlocking));
+        if (!ch->ev_commit) HIP_TRY(c, hipEventCreateWithFlags(&ch->ev_commit, hipEventDisableTiming));
+        if (on_device && !sl.ev_in) HIP_TRY(c, hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
+    }
+    // The slot's block: [seg_chain | sfirst | seg_flags | ent | pad to 16 | host table].
+    const uint64_t o_first = 4ull * ns, o_flags = o_first + 4ull * (ns + 1u), o_ent = o_flags + 4ull * ns;
+    const uint64_t o_tab = align16(o_ent + 4ull * entries);
+    const uint64_t bytes = o_tab + (on_device ? 0ull : 32ull * n_digests);
+    // Does a chain's FIRST segment lie in another wave than its LAST?  Then the
+    // FIRST lanes read a copy of the states taken ahead of the launch.
+    bool straddle = false;
+    uint8_t* rows = nullptr;
+    bool rows_direct = false;
+    if (ns) {
+        const uint32_t* plan = c->cm_plan.data();
+        uint32_t first_wave = 0;
+        for (uint32_t s = 0; s < ns && !straddle; s++) {
+            if (plan[o_pflags + s] & MIRSHA_COMMIT_SEG_FIRST) first_wave = s >> 6;
+            if ((plan[o_pflags + s] & MIRSHA_COMMIT_SEG_LAST) && (s >> 6) != first_wave) straddle = true;
+        }
+        HIP_TRY(c, cm.stage.ensure(bytes));
+        HIP_TRY(c, cm.dev.ensure(bytes));
+        if (straddle) HIP_TRY(c, cm.snap.ensure(72ull * ch->n));
+        if (values) {
+            // page-locked and 16-byte aligned: the kernel stores the values there itself
+            if (!(reinterpret_cast<uintptr_t>(values_out) & 15u) && kernel_writable_host(values_out, c->device)) {
+                void* dp = nullptr;
+                if (hipHostGetDevicePointer(&dp, values_out, 0) == hipSuccess)
+                    rows = static_cast<uint8_t*>(dp);
+                else
+                    (void)hipGetLastError();
+            }
+            rows_direct = rows != nullptr;
+            if (!rows) {
+                HIP_TRY(c, cm.rows.ensure(32ull * values));
+                void* dp = nullptr;
+                HIP_TRY(c, hipHostGetDevicePointer(&dp, cm.rows.p, 0));
+                rows = static_cast<uint8_t*>(dp);
+            }
+        }
+    }
+    ph[MIRSHA_PROF_PLAN] = ms_since(t0);
+    t0 = Clock::now();
+    auto queue = [&]() -> int {
+        const uint32_t* plan = c->cm_plan.data();
+        uint8_t* st = cm.stage.as<uint8_t>();
+        memcpy(st, plan, 4ull * ns);
+        memcpy(st + o_first, plan + o_pfirst, 4ull * (ns + 1u));
+        memcpy(st + o_flags, plan + o_pflags, 4ull * ns);
+        memcpy(st + o_ent, plan + o_pent, 4ull * entries);
+        if (!on_device && n_digests) memcpy(st + o_tab, digests, 32ull * n_digests);
+        hipStream_t q = c->xcommit;
+        if (on_device) {  // the table is read behind whatever was queued on the context's stream
+            HIP_TRY(c, hipEventRecord(sl.ev_in, c->stream));
+            HIP_TRY(c, hipStreamWaitEvent(q, sl.ev_in, 0));
+        }
+        HIP_TRY(c, hipMemcpyAsync(cm.dev.p, st, bytes, hipMemcpyHostToDevice, q));
+        uint32_t* h = ch->d_h.as<uint32_t>();
+        uint32_t* pend = ch->d_pend.as<uint32_t>();
+        uint64_t* cnt = ch->d_cnt.as<uint64_t>();
+        const uint32_t *h_in = h, *pend_in = pend;
+        const uint64_t* cnt_in = cnt;
+        if (straddle) {
+            uint8_t* sn = cm.snap.as<uint8_t>();
+            const uint64_t nc = ch->n;
+            HIP_TRY(c, hipMemcpyAsync(sn, h, 32ull * nc, hipMemcpyDeviceToDevice, q));
+            HIP_TRY(c, hipMemcpyAsync(sn + 32ull * nc, pend, 32ull * nc, hipMemcpyDeviceToDevice, q));
+            HIP_TRY(c, hipMemcpyAsync(sn + 64ull * nc, cnt, 8ull * nc, hipMemcpyDeviceToDevice, q));
+            h_in = reinterpret_cast<const uint32_t*>(sn);
+            pend_in = reinterpret_cast<const uint32_t*>(sn + 32ull * nc);
+            cnt_in = reinterpret_cast<const uint64_t*>(sn + 64ull * nc);
+        }
+        const uint8_t* dv = cm.dev.as<uint8_t>();
+        const uint8_t* d_dig = on_device ? digests : dv + o_tab;
+        const uint32_t prio = commit_seg_prio();
+        if (int rc = timed_launch(c, 1, [&] {
+                return mirsha::launch_chains_commit_seg(
+                    d_dig, reinterpret_cast<const uint32_t*>(dv + o_ent), reinterpret_cast<const uint32_t*>(dv),
+                    reinterpret_cast<const uint32_t*>(dv + o_first), reinterpret_cast<const uint32_t*>(dv + o_flags),
+                    ns, h_in, pend_in, cnt_in, h, pend, cnt, rows, prio, q);
+            }))
+            return rc;
+        HIP_TRY(c, hipEventRecord(sl.done, q));
+        HIP_TRY(c, hipEventRecord(ch->ev_commit, q));
+        return MIRSHA_OK;
+    };
+    if (ns) {
+        if (int rc = queue()) {
+            (void)hipStreamSynchronize(c->xcommit);  // what was queued reads this slot's buffers
+            return rc;
+        }
+        ch->commit_queued = true;
+    }
+    sl.t_queued = Clock::now();
+    ph[MIRSHA_PROF_PACK] = ms_since(t0);
+    sl.rank.clear();
+    sl.direct = false;
+    sl.xp.on = sl.xp.select = false;
+    cm.on = true;
+    cm.rows_direct = rows_direct;
+    cm.n_values = ns ? values : 0u;
+    cm.user_values = values_out;
+    sl.busy = true;
+    sl.user_out = nullptr;
+    sl.n = sl.m = 0;
+    sl.ticket = c->next_ticket++;
+    for (int k = 0; k < MIRSHA_PROF_PHASES; k++) sl.prof[k] = ph[k];
+    *n_values_out = values;
+    *ticket_out = sl.ticket;
+    return MIRSHA_OK;
+}
+
+}  // namespace
+
+}  // namespace mirsha_api
+
+extern "C" {
+
+int mirsha_chains_commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, uint32_t n_digests,
+                                const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
+                                uint8_t* values_out, uint32_t* n_values_out, uint64_t* ticket_out) {
+    return commit_submit(c, ch, digests, false, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out,
+                         ticket_out);
+}
+
+int mirsha_chains_commit_submit_device(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* d_digests, uint32_t n_digests,
+                                       const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
+                                       uint8_t* values_out, uint32_t* n_values_out, uint64_t* ticket_out) {
+    return commit_submit(c, ch, d_digests, true, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out,
+                         ticket_out);
+}
+
+}  // extern "C"

@@ -13,6 +13,8 @@
 //   mirsha_async.hip    the asynchronous ring (mirsha_submit_* / wait / poll,
 //                       dedup, mixed hash-and-verify cycles: *_expect)
 //   mirsha_expect.hip   the select kernel of the mixed submissions
+//   mirsha_commit_ring.hip  a cycle's Commits on the ring
+//                       (mirsha_chains_commit_submit*) and their segment kernel
 //   mirsha_multi.hip    the multi-device drop-in (mirsha_multi_*)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
@@ -51,6 +53,19 @@ namespace mirsha {
 hipError_t launch_expect_select(const uint8_t* digests, const uint8_t* expected, const uint64_t* has,
                                 const uint32_t* base, uint32_t n, uint8_t* out, uint64_t* bits, uint32_t* count,
                                 hipStream_t s);
+
+// mirsha_commit_ring.hip.  A cycle's commit programme cut into segments
+// (mirsha_commit_seg_plan's arrays), one lane per segment.  A FIRST segment
+// starts from its chain's state in h_in / pend_in / cnt_in (the chains' own
+// arrays, or a copy of them taken on the stream ahead of the launch), every
+// other one from Hasher(); a LAST segment stores the state it ends in to
+// h / pend / cnt.  Checkpoint values go to 32-byte rows of `out` (16-byte
+// aligned, device or host-visible memory) with plain vector stores.  `prio`:
+// the issue priority (0-3) the waves take at entry.
+hipError_t launch_chains_commit_seg(const uint8_t* digests, const uint32_t* ent, const uint32_t* seg_chain,
+                                    const uint32_t* sfirst, const uint32_t* seg_flags, uint32_t n_seg,
+                                    const uint32_t* h_in, const uint32_t* pend_in, const uint64_t* cnt_in, uint32_t* h,
+                                    uint32_t* pend, uint64_t* cnt, uint8_t* out, uint32_t prio, hipStream_t s);
 }  // namespace mirsha
 
 namespace mirsha_api {
@@ -141,6 +156,20 @@ struct ExpectSlot {
     DevBuf dev;         // stage's layout, then the verdict's (16-byte aligned)
 };
 
+// A commit submission (mirsha_chains_commit_submit*): the ring slot's own
+// copies of everything the device reads, so the caller's arrays are free when
+// the call returns.
+struct CommitSlot {
+    bool on = false;           // the ticket is a commit programme
+    bool rows_direct = false;  // the kernel stored the values into values_out itself
+    uint32_t n_values = 0;
+    uint8_t* user_values = nullptr;
+    PinnedBuf stage;  // [seg_chain | sfirst | seg_flags | ent | pad to 16 | host digest table]: ONE H2D
+    DevBuf dev;       // the same layout
+    DevBuf snap;      // [h | pend | cnt] as the launch found them (see commit_submit)
+    PinnedBuf rows;   // the values' rows when values_out is not kernel-writable
+};
+
 struct AsyncSlot {
     PinnedBuf stage;  // [arena bytes | off u64[m] | len u32[m] | order u32[m]]
     Clock::time_point t_queued;  // when its device work was queued
@@ -158,6 +187,7 @@ struct AsyncSlot {
     std::vector<uint32_t> rank;  // request -> row of `dig` (empty: identity)
     double prof[MIRSHA_PROF_PHASES] = {};  // this submission's host phases (published when it completes)
     ExpectSlot xp;
+    CommitSlot cm;
 };
 
 constexpr int kKernelTimers = 8;  // timing ids 0-7 (mirsha.h, mirsha_ctx_kernel_time)
@@ -211,6 +241,8 @@ struct mirsha_ctx {
     AsyncSlot slots[kAsyncSlots];
     std::vector<uint64_t> xp_has;   // mirsha_expect_plan of the submission being validated
     std::vector<uint32_t> xp_base;
+    hipStream_t xcommit = nullptr;  // commit submissions (created at the first one)
+    std::vector<uint32_t> cm_plan;  // mirsha_commit_seg_plan of the submission being validated
     uint64_t next_ticket = 1;  // ticket of the next submission
     uint64_t done_ticket = 0;  // every ticket <= this one has completed
     double prof[MIRSHA_PROF_PHASES] = {};  // host phases of the last slice submission (ms)
@@ -226,6 +258,10 @@ struct mirsha_chains {
     // [act | efirst | ent], one H2D copy (kept across calls).
     std::vector<uint32_t> plan;
     DevBuf d_plan;
+    // The last commit submission queued on this object (mirsha_chains_commit_submit*):
+    // the synchronous calls make their stream wait for it, destroy waits for it.
+    hipEvent_t ev_commit = nullptr;
+    bool commit_queued = false;
 };
 
 // A request -> batch-digest pipeline plan (see mirsha.h, mirsha_pipeline_create).
@@ -315,6 +351,14 @@ inline uint32_t host_blocks(uint32_t L) { return (uint32_t)(((uint64_t)L + 72u) 
 // order is the identity (one bucket).
 bool bucket_order(const uint32_t* len, uint32_t n, uint32_t* order);
 
+// Orders the context's stream behind the chains' last queued commit submission
+// (no host wait); nothing to do when there was none.
+inline int chains_order(mirsha_ctx* c, mirsha_chains* ch) {
+    if (!ch->commit_queued) return MIRSHA_OK;
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, ch->ev_commit, 0));
+    return MIRSHA_OK;
+}
+
 int check_lists(mirsha_ctx* c, const uint32_t* idx, const uint32_t* first, uint32_t n_lists, uint32_t n_digests);
 
 // Queues the device compare of n digests on c->stream: the count word is
@@ -391,6 +435,10 @@ int slice_args(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* s
                uint32_t n, const uint8_t* out);
 int slice_lengths(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
                   const uint32_t* slice_first, uint32_t n, const uint8_t* out, std::vector<uint32_t>& len);
+
+// ---- mirsha_async.hip
+// Retires every submission up to `ticket`, in ticket order.
+int async_wait_upto(mirsha_ctx* c, uint64_t ticket);
 
 // ---- mirsha_plan.hip
 int plan_build(mirsha_ctx* c, mirsha_pipeline* p, uint32_t n_req, const uint32_t* idx, const uint32_t* first,

@@ -811,3 +811,50 @@ extern "C" int mirsha_commit_plan(const uint32_t* op_chain, const uint32_t* op_d
     *n_values_out = rows;
     return MIRSHA_OK;
 }
+
+// mirsha_commit_plan's per-chain programmes cut after every checkpoint entry:
+// behind a checkpoint the chain restarts from Hasher(), so the stretches are
+// independent hashes (one lane each, mirsha_chains_commit_submit).  The
+// entries stay where mirsha_commit_plan put them; sfirst indexes them.
+extern "C" int mirsha_commit_seg_plan(const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
+                                      uint32_t n_chains, uint32_t n_digests, uint32_t* seg_chain_out,
+                                      uint32_t* sfirst_out, uint32_t* seg_flags_out, uint32_t* ent_out,
+                                      uint32_t* n_seg_out, uint32_t* n_active_out, uint32_t* n_entries_out,
+                                      uint32_t* n_values_out, uint32_t* bad_op_out) {
+    if (bad_op_out) *bad_op_out = UINT32_MAX;
+    if (!n_seg_out || !n_active_out || !n_entries_out || !n_values_out) return MIRSHA_EINVAL;
+    *n_seg_out = 0;
+    if (n_ops && (!seg_chain_out || !sfirst_out || !seg_flags_out || !ent_out)) {
+        // the argument checks of mirsha_commit_plan come first (its codes, its bad op)
+        const int rc = mirsha_commit_plan(op_chain, op_digest, n_ops, n_chains, n_digests, nullptr, nullptr, nullptr,
+                                          n_active_out, n_entries_out, n_values_out, bad_op_out);
+        return rc != MIRSHA_OK ? rc : MIRSHA_EINVAL;
+    }
+    const uint32_t cap = std::min(n_ops, n_chains);
+    std::vector<uint32_t> act, efirst;
+    try {
+        act.assign((size_t)cap, 0);
+        efirst.assign((size_t)cap + 1, 0);
+    } catch (const std::bad_alloc&) {
+        return MIRSHA_ENOMEM;
+    }
+    const int rc = mirsha_commit_plan(op_chain, op_digest, n_ops, n_chains, n_digests, act.data(), efirst.data(),
+                                      ent_out, n_active_out, n_entries_out, n_values_out, bad_op_out);
+    if (rc != MIRSHA_OK) return rc;
+    if (sfirst_out) sfirst_out[0] = 0;
+    uint32_t ns = 0;
+    for (uint32_t k = 0; k < *n_active_out; k++) {
+        const uint32_t e0 = efirst[k], e1 = efirst[k + 1];  // e1 > e0: the chain is active
+        uint32_t start = e0;
+        for (uint32_t e = e0; e < e1; e++) {
+            // a segment ends with a checkpoint entry, or with the chain's final entry
+            if (!(ent_out[e] & MIRSHA_COMMIT_ENTRY_CHECKPOINT) && e + 1 < e1) continue;
+            seg_chain_out[ns] = act[k];
+            seg_flags_out[ns] = (start == e0 ? MIRSHA_COMMIT_SEG_FIRST : 0u) | (e + 1 == e1 ? MIRSHA_COMMIT_SEG_LAST : 0u);
+            sfirst_out[++ns] = e + 1;
+            start = e + 1;
+        }
+    }
+    *n_seg_out = ns;
+    return MIRSHA_OK;
+}

@@ -124,6 +124,16 @@ class ExpectTicket(Ticket):
         self.mismatches = np.union1d(bad, self._short) if self._short.size else bad
 
 
+class CommitTicket(Ticket):
+    """A submission of CheckpointChains.submit_commit / submit_commit_device.
+    ``values`` (= ``out``), shape (k, 32): one row per checkpoint op, in op
+    order; complete after ``Engine.wait`` (or a ``poll`` that reports done)."""
+
+    @property
+    def values(self) -> np.ndarray:
+        return self.out
+
+
 def _out_rows(out, n: int) -> np.ndarray:
     """A caller-supplied (n, 32) uint8 result array (checked), or a new one."""
     if out is None:
@@ -229,6 +239,31 @@ def commit_plan(op_chain, op_digest, n_chains: int, n_digests: int):
         where = f"op {bad.value}" if bad.value != 0xFFFFFFFF else "arguments"
         raise MirshaError(rc, f"commit plan: {where}")
     return act[:na.value], efirst[:na.value + 1], ent[:ne.value], nv.value
+
+
+def commit_seg_plan(op_chain, op_digest, n_chains: int, n_digests: int):
+    """Host-only mirsha_commit_seg_plan: ``commit_plan``'s per-chain programmes
+    cut after every checkpoint entry, one segment per lane of the ring form
+    (``CheckpointChains.submit_commit``).  Returns (seg_chain, sfirst,
+    seg_flags, ent, n_values): segment s belongs to chain ``seg_chain[s]`` and
+    runs ``ent[sfirst[s]:sfirst[s+1]]`` (commit_plan's entries, unchanged);
+    ``seg_flags[s]`` has MIRSHA_COMMIT_SEG_FIRST on the chain's first segment
+    (it starts from the stored state, every other one from Hasher()) and
+    MIRSHA_COMMIT_SEG_LAST on the one holding the chain's final entry."""
+    oc, od = _commit_ops(op_chain, op_digest)
+    seg_chain = np.zeros(oc.size, dtype=np.uint32)
+    sfirst = np.zeros(oc.size + 1, dtype=np.uint32)
+    seg_flags = np.zeros(oc.size, dtype=np.uint32)
+    ent = np.zeros(oc.size, dtype=np.uint32)
+    ns, na, ne, nv, bad = (ctypes.c_uint32(0) for _ in range(5))
+    rc = _lib.load().mirsha_commit_seg_plan(_ptr(oc), _ptr(od), oc.size, int(n_chains), int(n_digests),
+                                            _ptr(seg_chain), sfirst.ctypes.data, _ptr(seg_flags), _ptr(ent),
+                                            ctypes.byref(ns), ctypes.byref(na), ctypes.byref(ne), ctypes.byref(nv),
+                                            ctypes.byref(bad))
+    if rc != _lib.MIRSHA_OK:
+        where = f"op {bad.value}" if bad.value != 0xFFFFFFFF else "arguments"
+        raise MirshaError(rc, f"commit segment plan: {where}")
+    return seg_chain[:ns.value], sfirst[:ns.value + 1], seg_flags[:ns.value], ent[:ne.value], nv.value
 
 
 def device_count() -> int:
@@ -753,6 +788,42 @@ class CheckpointChains:
             raise MirshaError(_lib.MIRSHA_EHIP, f"commit: {k.value} values for {out.shape[0]} checkpoints")
         return out
 
+    def submit_commit(self, digests, op_chain, op_digest, out=None) -> "CommitTicket":
+        """commit() as a submission of the engine's ring
+        (mirsha_chains_commit_submit): the programme is checked, planned and
+        copied before this returns, the device runs it on the engine's commit
+        stream beside whatever hashing is queued, and ``engine.wait(ticket)``
+        returns the checkpoint values, (k, 32) uint8 in op order.  Tickets
+        retire in submission order, mixed with the hashing tickets.  A
+        page-locked ``out`` (``engine.host_empty``) receives the values from
+        the kernel itself."""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        return self._submit(self._lib.mirsha_chains_commit_submit, _ptr(d), d.shape[0], op_chain, op_digest, out,
+                            None)
+
+    def submit_commit_device(self, d_digests: int, n_digests: int, op_chain, op_digest, out=None,
+                             keep=None) -> "CommitTicket":
+        """submit_commit() with the digest table in device memory (a raw device
+        address, 16-byte aligned): it is read behind whatever is queued on the
+        engine's stream at this moment, e.g. the ``hash_batch_device`` that
+        writes it, and must stay intact until the ticket retires (``keep``:
+        an object to hold on to until then)."""
+        return self._submit(self._lib.mirsha_chains_commit_submit_device, int(d_digests) or None, int(n_digests),
+                            op_chain, op_digest, out, keep)
+
+    def _submit(self, call, table, n_digests: int, op_chain, op_digest, out, keep) -> "CommitTicket":
+        oc, od = _commit_ops(op_chain, op_digest)
+        out = _out_rows(out, int(np.count_nonzero(od == _lib.MIRSHA_COMMIT_CHECKPOINT)))
+        k, t = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        eng = self._engine
+        eng._check(call(eng.ctx, self.handle, table, n_digests, _ptr(oc), _ptr(od), oc.size, _ptr(out),
+                        ctypes.byref(k), ctypes.byref(t)))
+        if k.value != out.shape[0]:
+            raise MirshaError(_lib.MIRSHA_EHIP, f"commit: {k.value} values for {out.shape[0]} checkpoints")
+        eng._outstanding[t.value] = (out, keep, self)  # the chains too: the kernel writes their state
+        eng._retire(t.value - ASYNC_SLOTS)
+        return CommitTicket(t.value, out)
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             self._lib.mirsha_chains_destroy(self.handle)
@@ -921,10 +992,12 @@ __all__ = [
     "SliceArrays",
     "Ticket",
     "ExpectTicket",
+    "CommitTicket",
     "dedup_plan",
     "expect_plan",
     "expect_bitmap",
     "commit_plan",
+    "commit_seg_plan",
     "MIRSHA_COMMIT_CHECKPOINT",
     "Pipeline",
     "bucket_order",

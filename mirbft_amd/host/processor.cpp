@@ -106,6 +106,22 @@ ActionResults make_results(const std::vector<const HashRequest*>& reqs,
 }
 }  // namespace
 
+namespace {
+std::vector<CheckpointResult> checkpoint_results(const std::vector<const Commit*>& commits,
+                                                 const std::vector<std::array<uint8_t, 32>>& values) {
+    std::vector<CheckpointResult> out;
+    for (const Commit* c : commits)
+        if (c->Checkpoint) {  // processor.go:164-167, commit order
+            CheckpointResult r;
+            r.Checkpoint = c->Checkpoint;
+            r.Commit = c;
+            r.Value = values.at(out.size());
+            out.push_back(r);
+        }
+    return out;
+}
+}  // namespace
+
 DeviceLog::DeviceLog(GpuEngine& engine, uint32_t n_nodes, uint32_t node)
     : engine_(engine), n_nodes_(n_nodes), node_(node) {
     if (node >= n_nodes) throw std::runtime_error("DeviceLog: node out of range");
@@ -115,10 +131,18 @@ DeviceLog::DeviceLog(GpuEngine& engine, uint32_t n_nodes, uint32_t node)
 
 DeviceLog::~DeviceLog() { mirsha_chains_destroy(chains_); }
 
-std::vector<std::array<uint8_t, 32>> DeviceLog::CommitCycle(const std::vector<const Commit*>& commits) {
-    // The cycle as one programme: each non-null request digest once in the
-    // table, each step as n_nodes consecutive ops (node 0 first).
+namespace {
+// The cycle as one programme: each non-null request digest once in the
+// table, each step as n_nodes consecutive ops (node 0 first).
+struct Programme {
     std::vector<uint8_t> table;
+    std::vector<uint32_t> op_chain, op_digest;
+    uint32_t checkpoints = 0;
+};
+
+Programme make_programme(const std::vector<const Commit*>& commits, uint32_t n_nodes) {
+    Programme p;
+    std::vector<uint8_t>& table = p.table;
     std::vector<uint32_t> prog;
     for (const Commit* c : commits) {
         if (!c || (c->Batch == nullptr) == (c->Checkpoint == nullptr))
@@ -137,41 +161,63 @@ std::vector<std::array<uint8_t, 32>> DeviceLog::CommitCycle(const std::vector<co
             table.insert(table.end(), d.data, d.data + 32);
         }
     }
-    std::vector<uint32_t> op_chain, op_digest;
-    uint32_t checkpoints = 0;
     for (uint32_t d : prog) {
-        checkpoints += d == MIRSHA_COMMIT_CHECKPOINT;
-        for (uint32_t node = 0; node < n_nodes_; node++) {
-            op_chain.push_back(node);
-            op_digest.push_back(d);
+        p.checkpoints += d == MIRSHA_COMMIT_CHECKPOINT;
+        for (uint32_t node = 0; node < n_nodes; node++) {
+            p.op_chain.push_back(node);
+            p.op_digest.push_back(d);
         }
     }
-    values_.assign((size_t)checkpoints * n_nodes_, {});
+    return p;
+}
+}  // namespace
+
+std::vector<std::array<uint8_t, 32>> DeviceLog::CommitCycle(const std::vector<const Commit*>& commits) {
+    const Programme p = make_programme(commits, n_nodes_);
+    values_.assign((size_t)p.checkpoints * n_nodes_, {});
     uint32_t k = 0;
-    int rc = mirsha_chains_commit(engine_.ctx(), chains_, table.data(), (uint32_t)(table.size() / 32), op_chain.data(),
-                                  op_digest.data(), (uint32_t)op_chain.size(),
+    int rc = mirsha_chains_commit(engine_.ctx(), chains_, p.table.data(), (uint32_t)(p.table.size() / 32),
+                                  p.op_chain.data(), p.op_digest.data(), (uint32_t)p.op_chain.size(),
                                   values_.empty() ? nullptr : values_[0].data(), &k);
     if (rc != MIRSHA_OK) panic(engine_.ctx(), rc, "could not commit");
     if (k != values_.size()) throw std::runtime_error("checkpoint count mismatch");
-    std::vector<std::array<uint8_t, 32>> mine(checkpoints);
-    for (uint32_t j = 0; j < checkpoints; j++) mine[j] = values_[(size_t)j * n_nodes_ + node_];
+    return Mine(values_);
+}
+
+std::vector<std::array<uint8_t, 32>> DeviceLog::Mine(const std::vector<std::array<uint8_t, 32>>& values) const {
+    std::vector<std::array<uint8_t, 32>> mine(values.size() / n_nodes_);
+    for (size_t j = 0; j < mine.size(); j++) mine[j] = values[j * n_nodes_ + node_];
     return mine;
+}
+
+uint64_t DeviceLog::SubmitCycle(const std::vector<const Commit*>& commits,
+                                std::vector<std::array<uint8_t, 32>>& values) {
+    // The library copies the programme and the table before it returns; only
+    // `values` must live until the ticket retires.
+    const Programme p = make_programme(commits, n_nodes_);
+    values.assign((size_t)p.checkpoints * n_nodes_, {});
+    uint32_t k = 0;
+    uint64_t ticket = 0;
+    int rc = mirsha_chains_commit_submit(engine_.ctx(), chains_, p.table.data(), (uint32_t)(p.table.size() / 32),
+                                         p.op_chain.data(), p.op_digest.data(), (uint32_t)p.op_chain.size(),
+                                         values.empty() ? nullptr : values[0].data(), &k, &ticket);
+    if (rc != MIRSHA_OK) panic(engine_.ctx(), rc, "could not submit the commits");
+    if (k != values.size()) throw std::runtime_error("checkpoint count mismatch");
+    return ticket;
+}
+
+std::vector<std::array<uint8_t, 32>> DeviceLog::CollectCycle(uint64_t ticket,
+                                                             const std::vector<std::array<uint8_t, 32>>& values) {
+    engine_.Wait(ticket);
+    values_ = values;
+    return Mine(values_);
 }
 
 std::vector<CheckpointResult> Processor::CommitLoop(const Actions& actions) {
     std::vector<CheckpointResult> out;
     if (actions.Commits.empty()) return out;
     if (!log_) throw std::runtime_error("actions.Commits without an application log");  // nil p.Log
-    const auto values = log_->CommitCycle(actions.Commits);
-    for (const Commit* c : actions.Commits)
-        if (c->Checkpoint) {  // processor.go:164-167, commit order
-            CheckpointResult r;
-            r.Checkpoint = c->Checkpoint;
-            r.Commit = c;
-            r.Value = values.at(out.size());
-            out.push_back(r);
-        }
-    return out;
+    return checkpoint_results(actions.Commits, log_->CommitCycle(actions.Commits));
 }
 
 ActionResults Processor::Process(const Actions& actions) {
@@ -184,10 +230,20 @@ ActionResults Processor::Process(const Actions& actions) {
 
 PendingResults Processor::Submit(const Actions& actions) {
     PendingResults p;
+    p.engine_ = &engine_;
     // Applied here, ahead of the hashing (neither reads the other's results):
     // cycles commit in submission order whatever the order of the Wait calls.
-    p.checkpoints_ = CommitLoop(actions);
-    p.engine_ = &engine_;
+    // With async_commits they are queued instead (commitInParallel beside
+    // hashInParallel, processor.go:447-470) and collected by Wait.
+    if (async_commits_ && !actions.Commits.empty()) {
+        if (!log_) throw std::runtime_error("actions.Commits without an application log");
+        p.values_ = std::make_unique<std::vector<std::array<uint8_t, 32>>>();
+        p.commit_ticket_ = log_->SubmitCycle(actions.Commits, *p.values_);
+        p.log_ = log_;
+        p.commits_ = actions.Commits;
+    } else {
+        p.checkpoints_ = CommitLoop(actions);
+    }
     p.reqs_ = actions.Hash;
     p.digests_ = std::make_unique<std::vector<std::array<uint8_t, 32>>>();
     if (!p.reqs_.empty()) p.ticket_ = engine_.Submit(p.reqs_, *p.digests_, dedup_);
@@ -196,11 +252,17 @@ PendingResults Processor::Submit(const Actions& actions) {
 
 PendingResults& PendingResults::operator=(PendingResults&& o) noexcept {
     if (this != &o) {
-        if (ticket_) {  // overwriting an uncollected cycle: let it land first
-            try { engine_->Wait(ticket_); } catch (...) {}
+        // overwriting an uncollected cycle: let it land first (tickets retire in order)
+        if (const uint64_t last = std::max(ticket_, commit_ticket_)) {
+            try { engine_->Wait(last); } catch (...) {}
         }
         engine_ = o.engine_;
         ticket_ = o.ticket_;
+        commit_ticket_ = o.commit_ticket_;
+        log_ = o.log_;
+        commits_ = std::move(o.commits_);
+        values_ = std::move(o.values_);
+        o.commit_ticket_ = 0;
         reqs_ = std::move(o.reqs_);
         digests_ = std::move(o.digests_);
         checkpoints_ = std::move(o.checkpoints_);
@@ -210,12 +272,16 @@ PendingResults& PendingResults::operator=(PendingResults&& o) noexcept {
 }
 
 PendingResults::~PendingResults() {
-    if (ticket_) {
-        try { engine_->Wait(ticket_); } catch (...) {}  // the buffer must outlive the library's write
+    if (const uint64_t last = std::max(ticket_, commit_ticket_)) {
+        try { engine_->Wait(last); } catch (...) {}  // the buffers must outlive the library's writes
     }
 }
 
 ActionResults PendingResults::Wait() {
+    if (commit_ticket_) {  // queued first, retired first
+        checkpoints_ = checkpoint_results(commits_, log_->CollectCycle(commit_ticket_, *values_));
+        commit_ticket_ = 0;
+    }
     if (ticket_) {
         engine_->Wait(ticket_);
         ticket_ = 0;
@@ -226,6 +292,8 @@ ActionResults PendingResults::Wait() {
 }
 
 }  // namespace mirbft
+
+extern "C" int mirbft_host_features(void) { return 1; }
 
 extern "C" int mirbft_host_process(int device, const uint8_t* const* data, const uint64_t* len, uint32_t n,
                                    uint8_t* digests_out, char* err, uint32_t err_len) {
@@ -283,7 +351,7 @@ extern "C" int mirbft_host_commit(int device, uint32_t n_nodes, const uint8_t* c
     try {
         mirbft::GpuEngine engine(device);
         mirbft::DeviceLog log(engine, n_nodes);
-        mirbft::Processor p(engine, false, &log);
+        mirbft::Processor p(engine, false, &log, (flags & 4) != 0);
         std::vector<mirbft::CommitBatch> batches(n_commits);
         std::vector<mirbft::Checkpoint> cps(n_commits);
         std::vector<mirbft::Commit> commits(n_commits);
@@ -303,6 +371,8 @@ extern "C" int mirbft_host_commit(int device, uint32_t n_nodes, const uint8_t* c
         mirbft::ActionResults r;
         if (flags & 2) {
             mirbft::PendingResults pending = p.Submit(a);
+            if (pending.CommitsQueued() != ((flags & 4) != 0 && n_commits != 0))
+                throw std::runtime_error("the commits were not queued as the option says");
             r = pending.Wait();
         } else {
             r = p.Process(a);

@@ -141,8 +141,18 @@ public:
     // checkpoint * n_nodes + node.
     std::vector<std::array<uint8_t, 32>> CommitCycle(const std::vector<const Commit*>& commits);
     const std::vector<std::array<uint8_t, 32>>& Values() const { return values_; }
+    // The asynchronous form (mirsha_chains_commit_submit): the cycle is queued
+    // as a ticket of the engine's ring and the call returns.  `values` (sized
+    // here, every node's rows) is written until the ticket retires and must
+    // live that long; CollectCycle waits for the ticket and returns what
+    // CommitCycle would have (Values() then holds that cycle's).  Cycles take
+    // effect in submission order, whatever the order they are collected in.
+    uint64_t SubmitCycle(const std::vector<const Commit*>& commits, std::vector<std::array<uint8_t, 32>>& values);
+    std::vector<std::array<uint8_t, 32>> CollectCycle(uint64_t ticket,
+                                                      const std::vector<std::array<uint8_t, 32>>& values);
 
 private:
+    std::vector<std::array<uint8_t, 32>> Mine(const std::vector<std::array<uint8_t, 32>>& values) const;
     GpuEngine& engine_;
     mirsha_chains* chains_ = nullptr;
     uint32_t n_nodes_, node_;
@@ -162,6 +172,8 @@ public:
     PendingResults& operator=(const PendingResults&) = delete;
     ~PendingResults();
     ActionResults Wait();
+    // async_commits: the cycle's commits are a ring ticket not yet collected.
+    bool CommitsQueued() const { return commit_ticket_ != 0; }
 
 private:
     friend class Processor;
@@ -170,12 +182,21 @@ private:
     std::vector<const HashRequest*> reqs_;
     std::unique_ptr<std::vector<std::array<uint8_t, 32>>> digests_;
     std::vector<CheckpointResult> checkpoints_;  // the commits were applied at Submit
+    // async_commits: the cycle's commit ticket, its Commits, and the buffer the
+    // library writes the checkpoint values into until that ticket retires.
+    uint64_t commit_ticket_ = 0;
+    DeviceLog* log_ = nullptr;
+    std::vector<const Commit*> commits_;
+    std::unique_ptr<std::vector<std::array<uint8_t, 32>>> values_;
 };
 
 class Processor {
 public:
-    explicit Processor(GpuEngine& engine, bool dedup = false, DeviceLog* log = nullptr)
-        : engine_(engine), dedup_(dedup), log_(log) {}
+    // async_commits: Submit queues the cycle's commits (DeviceLog::SubmitCycle)
+    // ahead of its hashing instead of applying them first; Wait collects
+    // them.  The ActionResults are the same either way.
+    explicit Processor(GpuEngine& engine, bool dedup = false, DeviceLog* log = nullptr, bool async_commits = false)
+        : engine_(engine), dedup_(dedup), log_(log), async_commits_(async_commits) {}
     // processor.go:129-143, batched; then the commit loop (:145-168) in one call.
     ActionResults Process(const Actions& actions);
     // Asynchronous Process: queue the cycle's hashing and return at once.
@@ -186,11 +207,15 @@ private:
     GpuEngine& engine_;
     bool dedup_;
     DeviceLog* log_;
+    bool async_commits_;
 };
 
 }  // namespace mirbft
 
 extern "C" {
+// What this build of the mirror offers beyond the first C entries: bit 0 = the
+// Processor's async_commits option (bit 2 of mirbft_host_commit's flags).
+int mirbft_host_features(void);
 // Small C entry for tests: hash n single-slice requests through
 // mirbft::Processor (exercises the C++ mirror end to end).
 int mirbft_host_process(int device, const uint8_t* const* data, const uint64_t* len, uint32_t n,
@@ -204,7 +229,8 @@ int mirbft_host_process_ex(int device, const uint8_t* const* data, const uint64_
 // batch_len[i] entries of digest_ptr (32 bytes each; NULL = a null request), or
 // a checkpoint if batch_len[i] == UINT32_MAX.  values_out: 32 bytes per
 // checkpoint and node (row checkpoint * n_nodes + node); flags bit 1 =
-// asynchronous (Submit, then Wait).
+// asynchronous (Submit, then Wait), bit 2 = the Processor's async_commits
+// option (with bit 1: the commits are a ring ticket of their own).
 int mirbft_host_commit(int device, uint32_t n_nodes, const uint8_t* const* digest_ptr, const uint32_t* batch_len,
                        uint32_t n_commits, uint8_t* values_out, uint32_t* n_checkpoints_out, int flags, char* err,
                        uint32_t err_len);

@@ -18,6 +18,11 @@ one kernel launch over the device-resident checkpoint chains
 (``CheckpointChains.commit``) -- and ``ActionResults.checkpoints`` holds one
 ``CheckpointResult`` per checkpoint, in commit order.  Commits without a log
 raise; a cycle without commits touches no log.
+``async_commits=True``: ``submit()`` (and so ``ProcessorWorkPool.process``)
+queues the cycle's commits as a ticket of the engine's ring
+(``DeviceLog.submit_cycle`` -> ``CheckpointChains.submit_commit``) ahead of the
+hashing instead of applying them first, and ``PendingResults.wait()`` collects
+them: commitInParallel beside hashInParallel (processor.go:447-470).
 
 ``Processor.process`` coalesces every HashRequest of one Ready() cycle into a
 single batched device call and returns ``Digests[i]`` for ``actions.hash[i]``
@@ -167,11 +172,18 @@ class DeviceLog:
     ``n_nodes = 1`` is a node's own log (chain 0); a testengine-style log
     drives the chains of n_nodes nodes, which commit the same entries, from the
     one cycle.  ``values`` keeps the last cycle's (checkpoints, n_nodes, 32)
-    array; ``commit_cycle`` returns node ``node``'s."""
+    array; ``commit_cycle`` returns node ``node``'s.
+
+    ``submit_cycle`` is the asynchronous form (``CheckpointChains.submit_commit``,
+    a ticket of the engine's ring): the cycle is queued and the call returns;
+    ``collect_cycle(ticket)`` waits for it and returns what ``commit_cycle``
+    would have.  Cycles take effect in submission order, whatever the order
+    they are collected in."""
 
     def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, chains=None):
         if not 0 <= node < n_nodes:
             raise ValueError(f"node {node} of {n_nodes}")
+        self._engine = engine
         self.n_nodes, self.node = int(n_nodes), int(node)
         self.chains = chains if chains is not None else CheckpointChains(engine, self.n_nodes)
         self.values = np.empty((0, self.n_nodes, 32), dtype=np.uint8)
@@ -179,6 +191,17 @@ class DeviceLog:
     def commit_cycle(self, commits) -> list:
         table, op_chain, op_digest = commit_programme(commits, self.n_nodes)
         self.values = self.chains.commit(table, op_chain, op_digest).reshape(-1, self.n_nodes, 32)
+        return [v.tobytes() for v in self.values[:, self.node]]
+
+    def submit_cycle(self, commits):
+        """Queues one cycle's commits; returns the ticket ``collect_cycle`` takes."""
+        table, op_chain, op_digest = commit_programme(commits, self.n_nodes)
+        return self.chains.submit_commit(table, op_chain, op_digest)
+
+    def collect_cycle(self, ticket) -> list:
+        """Waits for a cycle queued by ``submit_cycle``: node ``node``'s value
+        per checkpoint, in commit order; ``values`` holds every node's."""
+        self.values = self._engine.wait(ticket).reshape(-1, self.n_nodes, 32)
         return [v.tobytes() for v in self.values[:, self.node]]
 
     def close(self) -> None:
@@ -221,20 +244,32 @@ def _results(reqs, digests) -> ActionResults:
 class PendingResults:
     """Hash results of one submitted cycle; ``wait()`` returns its ActionResults."""
 
-    def __init__(self, engine: Engine, reqs, ticket, parts=None, checkpoints=None):
+    def __init__(self, engine: Engine, reqs, ticket, parts=None, checkpoints=None, commit=None):
         """``ticket``: the cycle's one submission, or None; ``parts`` instead:
         [(ticket, request indices)] of a cycle split over several submissions.
         ``checkpoints``: the cycle's CheckpointResults (its commits were applied
-        when it was submitted, so cycles commit in submission order)."""
+        when it was submitted, so cycles commit in submission order).
+        ``commit`` instead (``async_commits``): (log, ticket, the Commits that
+        ask for a checkpoint) of a cycle whose commits were queued with
+        ``log.submit_cycle``; ``wait()`` collects them."""
         self._engine, self._reqs, self._ticket = engine, reqs, ticket
         self._parts = parts
         self._checkpoints = checkpoints if checkpoints is not None else []
+        self._commit = commit
         self._results: Optional[ActionResults] = None
 
     def _tickets(self):
+        mine = [] if self._commit is None else [self._commit[1]]
         if self._parts is not None:
-            return [t for t, _ in self._parts]
-        return [] if self._ticket is None else [self._ticket]
+            return mine + [t for t, _ in self._parts]
+        return mine if self._ticket is None else mine + [self._ticket]
+
+    def _collect_commits(self) -> None:
+        if self._commit is None:
+            return
+        log, ticket, asked = self._commit
+        self._checkpoints = _checkpoint_results(asked, log.collect_cycle(ticket))
+        self._commit = None
 
     def done(self) -> bool:
         return self._results is not None or all(self._engine.poll(t) for t in self._tickets())
@@ -261,6 +296,7 @@ class PendingResults:
             if parts is None:
                 parts = [] if self._ticket is None else [(self._ticket, range(len(reqs)))]
             digests: list = [None] * len(reqs)
+            self._collect_commits()  # queued first, retired first
             for ticket, idx in parts:
                 self._part(ticket, idx, digests)
             # Digests[i] for actions.Hash[i] (processor.go:139)
@@ -270,18 +306,32 @@ class PendingResults:
         return self._results
 
 
+def _checkpoint_results(asked, values) -> list:
+    """Checkpoints in commit order, each pointing back at its Commit
+    (processor.go:164-167)."""
+    if len(values) != len(asked):
+        raise RuntimeError(f"the log returned {len(values)} values for {len(asked)} checkpoints")
+    return [CheckpointResult(checkpoint=c.checkpoint, value=bytes(v), commit=c) for c, v in zip(asked, values)]
+
+
 class Processor:
     """Hash stage of mirbft.Processor; batches one Ready() cycle per device call."""
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, dedup: bool = False,
-                 verify_on_device: bool = False, log=None):
+                 verify_on_device: bool = False, log=None, async_commits: bool = False):
         """``log``: the application log (p.Log, processor.go:147,163), e.g. a
         ``DeviceLog``: any object whose ``commit_cycle(commits)`` applies one
-        cycle's commits and returns one value per checkpoint among them."""
+        cycle's commits and returns one value per checkpoint among them.
+        ``async_commits``: ``submit()`` queues the cycle's commits
+        (``log.submit_cycle``, if the log has it) instead of applying them
+        before it queues the hashing, and ``PendingResults.wait()`` collects
+        them (``log.collect_cycle``): commitInParallel beside hashInParallel
+        (processor.go:447-470).  The ActionResults are the same either way."""
         self.engine = engine if engine is not None else Engine(device)
         self.dedup = dedup
         self.verify_on_device = verify_on_device
         self.log = log
+        self.async_commits = async_commits
 
     def process(self, actions: Actions) -> ActionResults:
         results = self._process_hash(actions.hash)  # the hash loop, then the commit loop
@@ -298,10 +348,20 @@ class Processor:
         if self.log is None:  # the reference dereferences a nil p.Log
             raise RuntimeError("actions.commits without an application log (Processor(log=...))")
         asked = [c for c in commits if c.checkpoint is not None]
-        values = self.log.commit_cycle(commits)
-        if len(values) != len(asked):
-            raise RuntimeError(f"the log returned {len(values)} values for {len(asked)} checkpoints")
-        return [CheckpointResult(checkpoint=c.checkpoint, value=bytes(v), commit=c) for c, v in zip(asked, values)]
+        return _checkpoint_results(asked, self.log.commit_cycle(commits))
+
+    def _submit_commits(self, actions):
+        """``async_commits``: the cycle's commits queued on the log, ahead of
+        the hashing (so cycles commit in submission order whatever the order of
+        the wait() calls).  Returns PendingResults' ``commit``, or None when
+        there is nothing to collect."""
+        commits = list(getattr(actions, "commits", None) or [])
+        if not commits:
+            return None
+        if self.log is None:
+            raise RuntimeError("actions.commits without an application log (Processor(log=...))")
+        asked = [c for c in commits if c.checkpoint is not None]
+        return (self.log, self.log.submit_cycle(commits), asked)
 
     def _process_hash(self, reqs) -> ActionResults:
         if not reqs:
@@ -339,15 +399,22 @@ class Processor:
         # The commits are applied here, synchronously and ahead of the hashing
         # (neither reads the other's results), so that cycles commit in
         # submission order whatever the order of the wait() calls.
-        cps = self._commit(actions)
+        # With async_commits they are queued instead (the log's ring ticket,
+        # ahead of the hashing tickets) and collected by wait().
+        cps, cm = None, None
+        if self.async_commits and hasattr(self.log, "submit_cycle"):
+            cm = self._submit_commits(actions)
+        else:
+            cps = self._commit(actions)
         if not reqs:
-            return PendingResults(self.engine, reqs, None, checkpoints=cps)
+            return PendingResults(self.engine, reqs, None, checkpoints=cps, commit=cm)
         if not self.verify_on_device:
             return PendingResults(self.engine, reqs, self.engine.submit_slices([r.data for r in reqs],
-                                                                               dedup=self.dedup), checkpoints=cps)
+                                                                               dedup=self.dedup), checkpoints=cps,
+                                  commit=cm)
         if not self.dedup:
             return PendingResults(self.engine, reqs, self.engine.submit_slices_expect(
-                [r.data for r in reqs], [r.expected for r in reqs]), checkpoints=cps)
+                [r.data for r in reqs], [r.expected for r in reqs]), checkpoints=cps, commit=cm)
         check = [i for i, r in enumerate(reqs) if r.expected is not None]
         plain = [i for i, r in enumerate(reqs) if r.expected is None]
         parts = []
@@ -356,7 +423,7 @@ class Processor:
                                                            [reqs[i].expected for i in check]), check))
         if plain:
             parts.append((self.engine.submit_slices([reqs[i].data for i in plain], dedup=True), plain))
-        return PendingResults(self.engine, reqs, None, parts, checkpoints=cps)
+        return PendingResults(self.engine, reqs, None, parts, checkpoints=cps, commit=cm)
 
 
 class ProcessorWorkPool(Processor):
@@ -367,8 +434,9 @@ class ProcessorWorkPool(Processor):
     """
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, hash_workers: int = 0,
-                 transmit_workers: int = 0, dedup: bool = False, verify_on_device: bool = False, log=None):
-        super().__init__(engine, device, dedup, verify_on_device, log)
+                 transmit_workers: int = 0, dedup: bool = False, verify_on_device: bool = False, log=None,
+                 async_commits: bool = False):
+        super().__init__(engine, device, dedup, verify_on_device, log, async_commits)
         self._mutex = threading.Lock()
         self.hash_workers = hash_workers
 
@@ -378,7 +446,9 @@ class ProcessorWorkPool(Processor):
         (the caller's persist / transmit work) runs while the GPU hashes, then
         the digests are collected in origin order -- with ``verify_on_device``
         too: the cycle's one mixed submission (``Processor.submit``) keeps the
-        overlap."""
+        overlap.  With ``async_commits`` the cycle's commits are queued ahead of
+        the hashing and collected with it: commits, hashing, ``overlap()``,
+        wait -- the reference's shape."""
         with self._mutex:  # processor.go:448-449
             pending = self.submit(actions)
             if overlap is not None:
