@@ -149,6 +149,16 @@ int mirsha_hash_slices_dedup(mirsha_ctx* ctx, const uint8_t* const* slice_ptr,
 int mirsha_dedup_plan(const uint8_t* const* slice_ptr, const uint64_t* slice_len,
                       const uint32_t* slice_first, uint32_t n, uint32_t* rep_out,
                       uint32_t* n_unique_out);
+/* Host-only as well: where each request's digest lies among the distinct
+ * requests' digests on the device, which is what
+ * mirsha_submit_slices_expect_dedup sends its select kernel.  row_out[i] in
+ * [0, *n_unique_out); row_out[i] == row_out[j] exactly when requests i and j
+ * have equal bytes.  The distinct requests of the scan's first segment take
+ * the lowest rows in origin order (they are hashed first), those found later
+ * follow.  Errors as mirsha_dedup_plan. */
+int mirsha_dedup_rows(const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                      const uint32_t* slice_first, uint32_t n, uint32_t* row_out,
+                      uint32_t* n_unique_out);
 
 /* Page-locked host memory for the caller's request arena.  The cgo binding
  * packs each Ready() cycle's request bytes into one C arena before the call
@@ -216,8 +226,9 @@ int mirsha_submit_batch(mirsha_ctx* ctx, const uint8_t* arena, uint64_t arena_le
  *   expected        32 m bytes, row k = the expectation of request
  *                   expect_of[k].  Both are read before the call returns and
  *                   travel H2D with the metadata;
- *   flags           must be 0 (MIRSHA_SUBMIT_DEDUP is MIRSHA_EINVAL: dedup and
- *                   expectations do not combine in one submission).
+ *   flags           must be 0 (MIRSHA_SUBMIT_DEDUP is MIRSHA_EINVAL here: a
+ *                   deduplicated cycle that carries expectations is
+ *                   mirsha_submit_slices_expect_dedup, below).
  * When the ticket retires (mirsha_wait, a mirsha_poll that reports done, or a
  * later submission reusing its ring slot):
  *   bits_out        (may be NULL) ceil(n / 64) words, bit i & 63 of word
@@ -253,6 +264,34 @@ int mirsha_hash_slices_expect(mirsha_ctx* ctx, const uint8_t* const* slice_ptr,
                               const uint64_t* slice_len, const uint32_t* slice_first, uint32_t n,
                               const uint32_t* expect_of, const uint8_t* expected, uint32_t m,
                               uint8_t* digests_out, uint64_t* bits_out, uint32_t* n_mismatch_out);
+/* The epoch-change cycle in ONE ticket: mirsha_submit_slices_expect (its
+ * argument rules, codes, messages, ticket and retirement) over a cycle that is
+ * deduplicated as mirsha_submit_slices(MIRSHA_SUBMIT_DEDUP) deduplicates it.
+ * Requests whose bytes are equal are hashed once, whether or not they carry
+ * an expectation; the select kernel reads request i's digest from the row of
+ * its representative (mirsha_dedup_rows) and compares it with request i's OWN
+ * expectation, so verdict and kept rows are exactly those of the plain mixed
+ * submission: bit i set iff request i carries an expectation and SHA-256 of
+ * its bytes differs from it; row i written for every request without an
+ * expectation and for every mismatch, duplicates included; a match's 32 bytes
+ * untouched.  No digest is copied back for the host to fan out.
+ * *n_unique_out (may be NULL) = distinct requests hashed, written before the
+ * call returns.  At most MIRSHA_MAX_DEVICE_ARENA_BYTES of distinct bytes per
+ * launch (the scan's first segment; the rest), as mirsha_hash_slices_dedup.
+ * mirsha_ctx_host_profile: validate = the scan plus the expectation plan,
+ * plan = the dedup plan plus the rows, the rest as above.
+ * mirsha_hash_slices_expect_dedup = submit + wait. */
+int mirsha_submit_slices_expect_dedup(mirsha_ctx* ctx, const uint8_t* const* slice_ptr,
+                                      const uint64_t* slice_len, const uint32_t* slice_first,
+                                      uint32_t n, const uint32_t* expect_of, const uint8_t* expected,
+                                      uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
+                                      uint32_t* n_mismatch_out, uint32_t* n_unique_out,
+                                      uint64_t* ticket_out);
+int mirsha_hash_slices_expect_dedup(mirsha_ctx* ctx, const uint8_t* const* slice_ptr,
+                                    const uint64_t* slice_len, const uint32_t* slice_first,
+                                    uint32_t n, const uint32_t* expect_of, const uint8_t* expected,
+                                    uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
+                                    uint32_t* n_mismatch_out, uint32_t* n_unique_out);
 /* Host-only (no device, no context), like mirsha_dedup_plan: the plan the
  * calls above send to the device.  has_out: ceil(n / 64) words, bit i & 63 of
  * word i >> 6 set exactly when request i is listed in expect_of; base_out[w] =

@@ -8,7 +8,7 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
 from .engine import (CheckpointChains, CommitTicket, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order,
-                     commit_plan, commit_seg_plan, dedup_plan, device_count, expect_bitmap, expect_plan, hash_batch_multi,
+                     commit_plan, commit_seg_plan, dedup_plan, dedup_rows, device_count, expect_bitmap, expect_plan, hash_batch_multi,
                      mismatch_indices)
 from .processor import (ActionResults, Actions, Checkpoint, CheckpointResult, Commit, CommitBatch, DeviceLog, GpuHash,
                         HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, commit_programme,
@@ -22,6 +22,7 @@ __all__ = [
     "ExpectTicket",
     "CommitTicket",
     "dedup_plan",
+    "dedup_rows",
     "expect_plan",
     "expect_bitmap",
     "commit_plan",

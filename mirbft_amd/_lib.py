@@ -79,6 +79,17 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p],
     ),
+    "mirsha_submit_slices_expect_dedup": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+         _u32p, _u64p],
+    ),
+    "mirsha_hash_slices_expect_dedup": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p,
+         _u32p],
+    ),
+    "mirsha_dedup_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, _u32p]),
     "mirsha_expect_plan": (c_int, [c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),
     "mirsha_hash_requests_then_batches": (
         c_int,

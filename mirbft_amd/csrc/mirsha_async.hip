@@ -1,5 +1,6 @@
 // mirsha_async.hip — the asynchronous, order-preserving ring
-// (mirsha_submit_slices / mirsha_wait / mirsha_poll, content-addressed dedup):
+// (mirsha_submit_slices / mirsha_wait / mirsha_poll, content-addressed dedup,
+// mixed hash-and-verify cycles, and the two in one ticket):
 // the hash stage of ProcessorWorkPool (processor.go:312-361, 447-470) without
 // its completion-order output.
 #include "mirsha_ctx.h"
@@ -14,14 +15,19 @@ struct ExpectArgs {
     uint32_t m;
     uint64_t* bits_out;
     uint32_t* n_mismatch_out;
+    bool dedup = false;  // mirsha_submit_slices_expect_dedup: one ticket, the select kernel gathers
 };
 
 // The argument checks of a mixed submission, and its plan (mirsha_expect_plan)
 // into the context's scratch.  Nothing is queued and no ticket is consumed.
 static int expect_validate(mirsha_ctx* c, const ExpectArgs& xa, uint32_t n, int flags) {
-    if (flags & MIRSHA_SUBMIT_DEDUP)
-        return fail(c, MIRSHA_EINVAL, "MIRSHA_SUBMIT_DEDUP does not combine with expectations");
-    if (flags) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
+    if (!xa.dedup) {  // the flags are the caller's
+        if (flags & MIRSHA_SUBMIT_DEDUP)
+            return fail(c, MIRSHA_EINVAL,
+                        "MIRSHA_SUBMIT_DEDUP does not combine with expectations here: "
+                        "mirsha_submit_slices_expect_dedup");
+        if (flags) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
+    }
     if (!xa.n_mismatch_out) return fail(c, MIRSHA_EINVAL, "n_mismatch_out is NULL");
     if (xa.m && (!xa.expect_of || !xa.expected)) return fail(c, MIRSHA_EINVAL, "NULL argument");
     if (xa.m > n) return fail(c, MIRSHA_EINVAL, "%u expectations for %u requests", xa.m, n);
@@ -45,13 +51,14 @@ static uint8_t* kernel_rows(mirsha_ctx* c, uint8_t* out) {
 
 // Sizes the (free) slot's expectation staging, device block and verdict, and
 // stages the plan.
-static int expect_stage(mirsha_ctx* c, AsyncSlot& sl, const ExpectArgs& xa, uint32_t n) {
+static int expect_stage(mirsha_ctx* c, AsyncSlot& sl, const ExpectArgs& xa, uint32_t n, bool gather = false) {
     ExpectSlot& x = sl.xp;
     x.words = (uint32_t)(((uint64_t)n + 63u) >> 6);
     x.o_exp = align16(12ull * x.words);
     x.h2d = x.o_exp + 32ull * xa.m;
-    x.o_ver = align16(x.h2d);
-    HIP_TRY(c, x.stage.ensure(std::max<uint64_t>(x.h2d, 16)));
+    x.o_row = align16(x.h2d);  // a deduplicated cycle's row_of[], sent on its own once it is resolved
+    x.o_ver = gather ? align16(x.o_row + 4ull * n) : x.o_row;
+    HIP_TRY(c, x.stage.ensure(std::max<uint64_t>(x.o_ver, 16)));
     HIP_TRY(c, x.verdict.ensure(8 + 8ull * x.words));
     HIP_TRY(c, x.dev.ensure(x.o_ver + 8 + 8ull * x.words));
     uint8_t* st = x.stage.as<uint8_t>();
@@ -75,16 +82,26 @@ static int expect_h2d(mirsha_ctx* c, AsyncSlot& sl, const ExpectArgs& xa, hipStr
 // Behind the hashing kernel on c->stream: the count's reset,
 // expect_select_kernel (timing id 7) over the n device digests, the kept rows
 // stored to `rows` (host-visible, device address), and the verdict's copy.
-static int expect_queue(mirsha_ctx* c, AsyncSlot& sl, const uint8_t* d_digests, uint32_t n, uint8_t* rows) {
+// A deduplicated cycle (`gather`): expect_select_gather_kernel instead, which
+// reads request i's digest from row row_of[i] (staged at o_row) of the
+// representatives' digests, rows [0, m0) in d_digests and the rest in d_digests2.
+static int expect_queue(mirsha_ctx* c, AsyncSlot& sl, const uint8_t* d_digests, uint32_t n, uint8_t* rows,
+                        bool gather = false, const uint8_t* d_digests2 = nullptr, uint32_t m0 = 0) {
     ExpectSlot& x = sl.xp;
     uint8_t* xd = x.dev.as<uint8_t>();
     uint32_t* d_count = reinterpret_cast<uint32_t*>(xd + x.o_ver);
     uint64_t* d_bits = reinterpret_cast<uint64_t*>(xd + x.o_ver + 8);
+    const uint64_t* d_has = reinterpret_cast<const uint64_t*>(xd);
+    const uint32_t* d_base = reinterpret_cast<const uint32_t*>(xd + 8ull * x.words);
     HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(uint32_t), c->stream));
     if (int rc = timed_launch(c, kTimerExpect, [&] {
-            return mirsha::launch_expect_select(d_digests, xd + x.o_exp, reinterpret_cast<const uint64_t*>(xd),
-                                                reinterpret_cast<const uint32_t*>(xd + 8ull * x.words), n, rows,
-                                                d_bits, d_count, c->stream);
+            if (gather)
+                return mirsha::launch_expect_select_gather(d_digests, d_digests2, m0,
+                                                           reinterpret_cast<const uint32_t*>(xd + x.o_row),
+                                                           xd + x.o_exp, d_has, d_base, n, rows, d_bits, d_count,
+                                                           c->stream);
+            return mirsha::launch_expect_select(d_digests, xd + x.o_exp, d_has, d_base, n, rows, d_bits, d_count,
+                                                c->stream);
         }))
         return rc;
     HIP_TRY(c, hipMemcpyAsync(x.verdict.p, xd + x.o_ver, 8 + 8ull * x.words, hipMemcpyDeviceToHost, c->stream));
@@ -191,10 +208,13 @@ int async_wait_upto(mirsha_ctx* c, uint64_t ticket) {
 int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
                  const uint32_t* slice_first, uint32_t n, uint8_t* out, int flags, uint64_t* ticket_out,
                  uint32_t* n_unique_out, const ExpectArgs* xa = nullptr) {
+    auto t0 = Clock::now();
     if (xa)
         if (int rc = expect_validate(c, *xa, n, flags)) return rc;
+    // a deduplicated mixed cycle counts its expectation plan as validation
+    const double t_xplan = xa && xa->dedup ? ms_since(t0) : 0.0;
     if (flags & ~MIRSHA_SUBMIT_DEDUP) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
-    auto t0 = Clock::now();
+    t0 = Clock::now();
     // Which requests reach the GPU: all, or one per distinct content.  With
     // dedup the requests are scanned in segments in origin order
     // (mirsha::host::DedupScan): the first segment's heads (distinct
@@ -213,7 +233,7 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     } else if (n) {
         if (int rc = slice_lengths(c, slice_ptr, slice_len, slice_first, n, out, len)) return rc;
     }
-    ph[MIRSHA_PROF_VALIDATE] = ms_since(t0);
+    ph[MIRSHA_PROF_VALIDATE] = ms_since(t0) + t_xplan;
     t0 = Clock::now();
     if (int rc = use_device(c)) return rc;
     AsyncSlot& sl = c->slots[(c->next_ticket - 1) % kAsyncSlots];
@@ -228,10 +248,16 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     // Mixed submission with expectations: the select kernel stands where the
     // digests' D2H copy stood, storing the kept rows into a page-locked
     // digests_out or else into the slot's page-locked rows.
+    // Deduplicated as well (`gather`): every launch keeps its representatives'
+    // digests on the device, the expectation block goes H2D once behind the
+    // first launch's request bytes, and ONE select launch behind the last
+    // hashing launch reads request i's digest from row row_of[i].
     const bool sel = xa && xa->m;
+    const bool gather = sel && dedup;
+    const uint8_t* gather_dig[2] = {nullptr, nullptr};  // the launches' digest rows on the device
     uint8_t* sel_rows = nullptr;
     if (sel) {
-        if (int rc = expect_stage(c, sl, *xa, n)) return rc;
+        if (int rc = expect_stage(c, sl, *xa, n, gather)) return rc;
         sel_rows = kernel_rows(c, out);
         sl.xp.rows_direct = sel_rows != nullptr;
         if (!sel_rows)
@@ -270,7 +296,7 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
         uint8_t* dv = dev.as<uint8_t>();
         if (m) {
             HIP_TRY(c, hipMemcpyAsync(dv, st, o_end, hipMemcpyHostToDevice, c->stream));
-            if (sel)
+            if (sel && !(gather && row0))
                 if (int rc = expect_h2d(c, sl, *xa, c->stream)) return rc;
             int rc = timed_launch(c, 0, [&] {
                 return mirsha::launch_msgs(dv, bytes, reinterpret_cast<const uint64_t*>(dv + o_off),
@@ -279,7 +305,9 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
                                            dv + o_dig, c->variant, c->stream);
             });
             if (rc) return rc;
-            if (sel) {
+            if (gather) {
+                gather_dig[row0 ? 1 : 0] = dv + o_dig;
+            } else if (sel) {
                 if (int rc2 = expect_queue(c, sl, dv + o_dig, m, sel_rows)) return rc2;
             } else {
                 HIP_TRY(c, hipMemcpyAsync(sl.dig.as<uint8_t>() + 32ull * row0, dv + o_dig, 32ull * m,
@@ -328,18 +356,35 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
         const uint32_t m0 = (uint32_t)first_heads.size();
         m = m0 + (uint32_t)later.size();
         if (m != distinct) return fail(c, MIRSHA_EHIP, "dedup: %u representatives for %u contents", m, distinct);
-        sl.rank.resize(n);
-        for (uint32_t k = 0; k < m0; k++) sl.rank[first_heads[k]] = k;
-        for (uint32_t k = 0; k < (uint32_t)later.size(); k++) sl.rank[later[k]] = m0 + k;
-        bool identity = true;
-        for (uint32_t i = 0; i < n; i++) {
-            sl.rank[i] = sl.rank[rep[i]];
-            identity &= sl.rank[i] == i;
+        // request -> row of the representatives' digests: for the host's fan-out
+        // at retirement, or (gather) into the expectation staging for the kernel's
+        uint32_t* row_of = nullptr;
+        if (gather) {
+            row_of = reinterpret_cast<uint32_t*>(sl.xp.stage.as<uint8_t>() + sl.xp.o_row);
+        } else {
+            sl.rank.resize(n);
+            row_of = sl.rank.data();
         }
-        if (identity) sl.rank.clear();  // all distinct, rows already in origin order
+        const bool identity = mirsha::host::dedup_rows(rep.data(), first_heads, later, n, row_of);
+        if (identity && !gather) sl.rank.clear();  // all distinct, rows already in origin order
+        if (gather) {  // the kernel's loads stay inside the m rows
+            uint32_t top = 0;
+            for (uint32_t i = 0; i < n; i++) top = std::max(top, row_of[i]);
+            if (top >= m) {
+                HIP_TRY(c, hipStreamSynchronize(c->stream));  // the first launch reads this slot's buffers
+                return fail(c, MIRSHA_EHIP, "dedup: row %u of %u representatives", top, m);
+            }
+        }
         ph[MIRSHA_PROF_PLAN] += ms_since(t0);
         if (!later.empty())
             if (int rc = queue(later.data(), (uint32_t)later.size(), m0, sl.stage2, sl.dev2)) return rc;
+        if (gather) {
+            const auto tq = Clock::now();
+            HIP_TRY(c, hipMemcpyAsync(sl.xp.dev.as<uint8_t>() + sl.xp.o_row, row_of, 4ull * n, hipMemcpyHostToDevice,
+                                      c->stream));
+            if (int rc = expect_queue(c, sl, gather_dig[0], n, sel_rows, true, gather_dig[1], m0)) return rc;
+            ph[MIRSHA_PROF_PACK] += ms_since(tq);
+        }
     }
     if (n_unique_out) *n_unique_out = m;
     HIP_TRY(c, hipEventRecord(sl.done, c->stream));
@@ -703,6 +748,29 @@ int mirsha_hash_slices_expect(mirsha_ctx* c, const uint8_t* const* slice_ptr, co
     uint64_t t = 0;
     const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
     if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, 0, &t, nullptr, &xa)) return rc;
+    return async_wait_upto(c, t);
+}
+
+int mirsha_submit_slices_expect_dedup(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                                      const uint32_t* slice_first, uint32_t n, const uint32_t* expect_of,
+                                      const uint8_t* expected, uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
+                                      uint32_t* n_mismatch_out, uint32_t* n_unique_out, uint64_t* ticket_out) {
+    if (!c || !ticket_out) return MIRSHA_EINVAL;
+    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out, true};
+    return async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, MIRSHA_SUBMIT_DEDUP, ticket_out,
+                        n_unique_out, &xa);
+}
+
+int mirsha_hash_slices_expect_dedup(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                                    const uint32_t* slice_first, uint32_t n, const uint32_t* expect_of,
+                                    const uint8_t* expected, uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
+                                    uint32_t* n_mismatch_out, uint32_t* n_unique_out) {
+    if (!c) return MIRSHA_EINVAL;
+    uint64_t t = 0;
+    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out, true};
+    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, MIRSHA_SUBMIT_DEDUP, &t,
+                              n_unique_out, &xa))
+        return rc;
     return async_wait_upto(c, t);
 }
 

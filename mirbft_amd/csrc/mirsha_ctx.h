@@ -11,8 +11,9 @@
 //   mirsha_plan.hip     request -> batch plans: sequential, fused (placement
 //                       probe), overlapped cycles (mirsha_pipeline_*)
 //   mirsha_async.hip    the asynchronous ring (mirsha_submit_* / wait / poll,
-//                       dedup, mixed hash-and-verify cycles: *_expect)
-//   mirsha_expect.hip   the select kernel of the mixed submissions
+//                       dedup, mixed hash-and-verify cycles: *_expect,
+//                       both in one ticket: *_expect_dedup)
+//   mirsha_expect.hip   the select kernels of the mixed submissions
 //   mirsha_commit_ring.hip  a cycle's Commits on the ring
 //                       (mirsha_chains_commit_submit*) and their segment kernel
 //   mirsha_multi.hip    the multi-device drop-in (mirsha_multi_*)
@@ -53,6 +54,14 @@ namespace mirsha {
 hipError_t launch_expect_select(const uint8_t* digests, const uint8_t* expected, const uint64_t* has,
                                 const uint32_t* base, uint32_t n, uint8_t* out, uint64_t* bits, uint32_t* count,
                                 hipStream_t s);
+// The same over a deduplicated cycle (mirsha_submit_slices_expect_dedup):
+// request i's digest is row row_of[i] (< m, the caller checked) of the
+// representatives' digests, rows [0, m0) in digests0 and [m0, m) in digests1
+// (may be NULL when m0 = m).
+hipError_t launch_expect_select_gather(const uint8_t* digests0, const uint8_t* digests1, uint32_t m0,
+                                       const uint32_t* row_of, const uint8_t* expected, const uint64_t* has,
+                                       const uint32_t* base, uint32_t n, uint8_t* out, uint64_t* bits,
+                                       uint32_t* count, hipStream_t s);
 
 // mirsha_commit_ring.hip.  A cycle's commit programme cut into segments
 // (mirsha_commit_seg_plan's arrays), one lane per segment.  A FIRST segment
@@ -149,9 +158,10 @@ struct ExpectSlot {
     bool rows_direct = false;  // the kernel stored the kept rows into digests_out itself
     uint32_t words = 0;   // ceil(n / 64)
     uint64_t o_exp = 0, o_ver = 0, h2d = 0;  // offsets of the expected rows and the verdict; bytes of `stage`
+    uint64_t o_row = 0;  // offset of row_of u32[n] (a deduplicated mixed submission), behind the expected rows
     uint64_t* user_bits = nullptr;
     uint32_t* user_count = nullptr;
-    PinnedBuf stage;    // [has u64[words] | base u32[words], padded to 16 | expected 32 m]: H2D source
+    PinnedBuf stage;    // [has u64[words] | base u32[words], padded to 16 | expected 32 m | row_of]: H2D source
     PinnedBuf verdict;  // [count u32, pad | mismatch bitmap u64[words]]: D2H target
     DevBuf dev;         // stage's layout, then the verdict's (16-byte aligned)
 };

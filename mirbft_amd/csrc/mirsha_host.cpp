@@ -568,6 +568,19 @@ uint32_t dedup_plan(const uint8_t* const* ptr, const uint64_t* len, const uint32
     return d.resolve(rep, nullptr);
 }
 
+bool dedup_rows(const uint32_t* rep, const std::vector<uint32_t>& heads0, const std::vector<uint32_t>& later,
+                uint32_t n, uint32_t* row) {
+    const uint32_t m0 = (uint32_t)heads0.size();
+    for (uint32_t k = 0; k < m0; k++) row[heads0[k]] = k;
+    for (uint32_t k = 0; k < (uint32_t)later.size(); k++) row[later[k]] = m0 + k;
+    bool identity = true;
+    for (uint32_t i = 0; i < n; i++) {  // rep[i] <= i: a representative's row is final when it is read
+        row[i] = row[rep[i]];
+        identity &= row[i] == i;
+    }
+    return identity;
+}
+
 namespace {
 // memcpy whose body bypasses the CPU caches (16-byte non-temporal stores):
 // page-locked staging written this way DMAs at the link's 57.4 GB/s, written
@@ -712,6 +725,33 @@ extern "C" int mirsha_dedup_plan(const uint8_t* const* slice_ptr, const uint64_t
     if (slice_first[n] && (!slice_ptr || !slice_len)) return MIRSHA_EINVAL;
     const uint32_t u = mirsha::host::dedup_plan(slice_ptr, slice_len, slice_first, n, rep_out, nullptr, nullptr);
     if (u == UINT32_MAX) return MIRSHA_EINVAL;  // slice_first not monotone / a NULL slice with bytes
+    if (n_unique_out) *n_unique_out = u;
+    return MIRSHA_OK;
+}
+
+// The scan of a dedup submission (async_submit) without its launches: the first
+// segment's heads take the first launch's rows, later heads and collisions the
+// second's.
+extern "C" int mirsha_dedup_rows(const uint8_t* const* slice_ptr, const uint64_t* slice_len,
+                                 const uint32_t* slice_first, uint32_t n, uint32_t* row_out,
+                                 uint32_t* n_unique_out) {
+    if (n == 0) {
+        if (n_unique_out) *n_unique_out = 0;
+        return MIRSHA_OK;
+    }
+    if (!slice_first || !row_out || slice_first[0] != 0) return MIRSHA_EINVAL;
+    if (slice_first[n] && (!slice_ptr || !slice_len)) return MIRSHA_EINVAL;
+    mirsha::host::DedupScan d(slice_ptr, slice_len, slice_first, n, ~0ull);
+    const std::vector<uint32_t> seg = d.segments();
+    std::vector<uint32_t> heads0, later;
+    for (size_t k = 0; k + 1 < seg.size(); k++) {
+        if (!d.scan(seg[k], seg[k + 1])) return MIRSHA_EINVAL;  // slice_first not monotone / a NULL slice with bytes
+        d.assign(seg[k], seg[k + 1], k == 0 ? heads0 : later);
+        d.confirm(seg[k], seg[k + 1]);
+    }
+    std::vector<uint32_t> rep(n);
+    const uint32_t u = d.resolve(rep.data(), &later);
+    mirsha::host::dedup_rows(rep.data(), heads0, later, n, row_out);
     if (n_unique_out) *n_unique_out = u;
     return MIRSHA_OK;
 }

@@ -112,6 +112,14 @@ class DedupScan {
 uint32_t dedup_plan(const uint8_t* const* ptr, const uint64_t* len, const uint32_t* first, uint32_t n,
                     uint32_t* rep, const uint8_t** err_out, std::vector<uint8_t>* err);
 
+// Where each request's digest lies among the representatives' digests of a
+// dedup submission: the first launch hashes `heads0` (the first segment's
+// heads) into rows [0, |heads0|), the second `later` (heads of later segments,
+// then collisions) into the rows behind them; row[i] = the row of rep[i].
+// True if row[] is the identity (all distinct, in origin order).
+bool dedup_rows(const uint32_t* rep, const std::vector<uint32_t>& heads0, const std::vector<uint32_t>& later,
+                uint32_t n, uint32_t* row);
+
 // Copies request which[k] (k < m) to dst + dst_off[k], in parallel.  With
 // `stream` the stores bypass the CPU caches (non-temporal, fenced before
 // return): for page-locked staging a DMA reads next, which then runs at the

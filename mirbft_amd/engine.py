@@ -106,12 +106,14 @@ class ExpectTicket(Ticket):
     that reports done) ``mismatches`` holds the sorted indices whose digest
     differs from their expectation, and ``out[i]`` the digest of every request
     without an expectation and of every mismatch; the row of a matching
-    request is NOT written (its digest equals the expectation passed in)."""
+    request is NOT written (its digest equals the expectation passed in).
+    ``n_unique``: the distinct requests hashed (submit_slices_expect_dedup), else None."""
 
     def __init__(self, value: int, out: np.ndarray, has: np.ndarray, bits: np.ndarray, count: np.ndarray,
-                 short: np.ndarray):
+                 short: np.ndarray, n_unique: int | None = None):
         super().__init__(value, out)
         self.has = has
+        self.n_unique = n_unique
         self.mismatches: np.ndarray | None = None
         self._bits, self._count, self._short = bits, count, short
 
@@ -209,6 +211,17 @@ def dedup_plan(requests) -> tuple[np.ndarray, int]:
     rc = _lib.load().mirsha_dedup_plan(sl.ptr_p, sl.len_p, sl.first_p, sl.n, _ptr(rep), ctypes.byref(u))
     check(rc)
     return rep, u.value
+
+
+def dedup_rows(requests) -> tuple[np.ndarray, int]:
+    """Host-only (mirsha_dedup_rows): row[i] = where request i's digest lies among
+    the distinct requests' digests of a submit_slices_expect_dedup call (equal
+    bytes, equal row); returns (row, number of distinct requests)."""
+    sl = requests if isinstance(requests, SliceArrays) else SliceArrays.from_requests(requests)
+    row = np.empty(sl.n, dtype=np.uint32)
+    u = ctypes.c_uint32(0)
+    check(_lib.load().mirsha_dedup_rows(sl.ptr_p, sl.len_p, sl.first_p, sl.n, _ptr(row), ctypes.byref(u)))
+    return row, u.value
 
 
 def _commit_ops(op_chain, op_digest) -> tuple[np.ndarray, np.ndarray]:
@@ -460,6 +473,42 @@ class Engine:
         self._outstanding[t.value] = (out, bits, count, of, rows, keep)
         self._retire(t.value - ASYNC_SLOTS)
         return ExpectTicket(t.value, out, has, bits, count, short)
+
+    def submit_slices_expect_dedup(self, requests, expected, out=None) -> "ExpectTicket":
+        """submit_slices_expect over a deduplicated cycle
+        (mirsha_submit_slices_expect_dedup): equal requests are hashed once,
+        with or without an expectation, and each is compared with its own
+        expectation on the device.  ONE ring submission; the ticket, verdict
+        and kept rows of submit_slices_expect, plus ``ticket.n_unique``."""
+        sl = requests if isinstance(requests, SliceArrays) else SliceArrays.from_requests(requests)
+        u = ctypes.c_uint32(0)
+        ticket = self._expect_ticket(
+            lambda of, rows, m, o, bits, count, t: self._lib.mirsha_submit_slices_expect_dedup(
+                self.ctx, sl.ptr_p, sl.len_p, sl.first_p, sl.n, of, rows, m, o, bits, count, ctypes.byref(u), t),
+            sl.n, expected, out, sl)
+        ticket.n_unique = u.value
+        return ticket
+
+    @staticmethod
+    def dedup_rows(requests) -> tuple[np.ndarray, int]:
+        """The module's dedup_rows: the rows submit_slices_expect_dedup sends."""
+        return dedup_rows(requests)
+
+    def hash_slices_expect_dedup(self, requests, expected, out=None) -> "ExpectTicket":
+        """submit_slices_expect_dedup + wait in one call
+        (mirsha_hash_slices_expect_dedup): the retired ticket, ``mismatches``
+        and ``n_unique`` set."""
+        sl = requests if isinstance(requests, SliceArrays) else SliceArrays.from_requests(requests)
+        u = ctypes.c_uint32(0)
+        # the call hands no ticket out (it retired its own): value 0
+        ticket = self._expect_ticket(
+            lambda of, rows, m, o, bits, count, t: self._lib.mirsha_hash_slices_expect_dedup(
+                self.ctx, sl.ptr_p, sl.len_p, sl.first_p, sl.n, of, rows, m, o, bits, count, ctypes.byref(u)),
+            sl.n, expected, out, sl)
+        self._outstanding.pop(ticket.value, None)
+        ticket.n_unique = u.value
+        ticket._resolve()
+        return ticket
 
     def submit_slices_expect(self, requests, expected, out=None) -> "ExpectTicket":
         """submit_slices for a cycle whose requests may carry the digest their
@@ -994,6 +1043,7 @@ __all__ = [
     "ExpectTicket",
     "CommitTicket",
     "dedup_plan",
+    "dedup_rows",
     "expect_plan",
     "expect_bitmap",
     "commit_plan",

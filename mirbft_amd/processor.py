@@ -48,9 +48,11 @@ off.  ``submit()`` (and so ``ProcessorWorkPool.process``) makes ONE ring
 submission for the whole cycle, whatever it holds
 (``Engine.submit_slices_expect``: the compare runs behind the hashing kernel,
 and the digests of the requests without an expectation and of the mismatches
-come back with the verdict); with ``dedup=True`` as well, the requests that
-carry an expectation go in one such submission and the rest in one
-``submit_slices(dedup=True)``.  ``process()`` keeps its synchronous split
+come back with the verdict); with ``dedup=True`` as well it is still one:
+``Engine.submit_slices_expect_dedup`` hashes each distinct content once,
+expectation or not, and its select kernel reads every request's digest from
+its representative's row (a cycle without any expectation stays one
+``submit_slices(dedup=True)``).  ``process()`` keeps its synchronous split
 (``Engine.verify_slices`` for the requests with an expectation,
 ``hash_slices`` for the rest and, again, for the mismatches): above 32 MiB it
 takes the pipelined staging route, which the ring does not have.
@@ -392,9 +394,12 @@ class Processor:
     def submit(self, actions: Actions) -> PendingResults:
         """Asynchronous process(): queue the cycle's hashing, return at once.
         With ``verify_on_device`` the whole cycle is ONE mixed submission
-        (``submit_slices_expect``); with ``dedup`` as well, the requests that
-        carry an expectation are one such submission and the rest one
-        ``submit_slices(dedup=True)`` (the two do not combine in one)."""
+        (``submit_slices_expect``); with ``dedup`` as well it is ONE
+        deduplicated mixed submission (``submit_slices_expect_dedup``) when the
+        cycle holds an expectation, else one ``submit_slices(dedup=True)``.
+        An engine without ``submit_slices_expect_dedup`` gets the requests that
+        carry an expectation in one ``submit_slices_expect`` and the rest in one
+        ``submit_slices(dedup=True)``."""
         reqs = list(actions.hash)
         # The commits are applied here, synchronously and ahead of the hashing
         # (neither reads the other's results), so that cycles commit in
@@ -417,6 +422,9 @@ class Processor:
                 [r.data for r in reqs], [r.expected for r in reqs]), checkpoints=cps, commit=cm)
         check = [i for i, r in enumerate(reqs) if r.expected is not None]
         plain = [i for i, r in enumerate(reqs) if r.expected is None]
+        if check and hasattr(self.engine, "submit_slices_expect_dedup"):
+            return PendingResults(self.engine, reqs, self.engine.submit_slices_expect_dedup(
+                [r.data for r in reqs], [r.expected for r in reqs]), checkpoints=cps, commit=cm)
         parts = []
         if check:
             parts.append((self.engine.submit_slices_expect([reqs[i].data for i in check],
