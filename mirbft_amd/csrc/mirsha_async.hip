@@ -7,6 +7,45 @@
 
 namespace mirsha_api {
 
+// ---- the slot lifecycle (mirsha_ctx.h) ---------------------------------------
+int ensure_event(mirsha_ctx* c, hipEvent_t* e) {
+    if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    return MIRSHA_OK;
+}
+
+int ring_acquire(mirsha_ctx* c, AsyncSlot** slot) {
+    if (int rc = use_device(c)) return rc;
+    AsyncSlot& sl = c->slots[(c->next_ticket - 1) % kAsyncSlots];
+    if (sl.busy)
+        if (int rc = async_wait_upto(c, sl.ticket)) return rc;  // ring full: retire the oldest
+    sl.retire = SlotRetire{};
+    *slot = &sl;
+    return ensure_event(c, &sl.done);
+}
+
+void ring_publish(mirsha_ctx* c, AsyncSlot& sl, RingQueued& queued, const double* ph, uint64_t* ticket_out) {
+    queued.armed = false;
+    sl.busy = true;
+    sl.ticket = c->next_ticket++;
+    for (int k = 0; k < MIRSHA_PROF_PHASES; k++) sl.prof[k] = ph[k];
+    if (ticket_out) *ticket_out = sl.ticket;
+}
+
+uint8_t* host_rows(mirsha_ctx* c, void* p) {
+    if (!p || (reinterpret_cast<uintptr_t>(p) & 15u) || !kernel_writable_host(p, c->device)) return nullptr;
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, p, 0) == hipSuccess) return static_cast<uint8_t*>(dp);
+    (void)hipGetLastError();
+    return nullptr;
+}
+
+int pinned_rows(mirsha_ctx* c, const PinnedBuf& b, uint8_t** rows) {
+    void* dp = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer(&dp, b.p, 0));
+    *rows = static_cast<uint8_t*>(dp);
+    return MIRSHA_OK;
+}
+
 // ---- mixed hash-and-verify cycles (mirsha_submit_*_expect) -------------------
 // What a mixed submission adds to the plain one's arguments.
 struct ExpectArgs {
@@ -15,19 +54,22 @@ struct ExpectArgs {
     uint32_t m;
     uint64_t* bits_out;
     uint32_t* n_mismatch_out;
-    bool dedup = false;  // mirsha_submit_slices_expect_dedup: one ticket, the select kernel gathers
 };
+
+// The one check of a caller's submit flags: mirsha_submit_slices takes
+// MIRSHA_SUBMIT_DEDUP, mirsha_submit_slices_expect (`mixed`) none.
+static int check_submit_flags(mirsha_ctx* c, int flags, bool mixed) {
+    if (mixed && (flags & MIRSHA_SUBMIT_DEDUP))
+        return fail(c, MIRSHA_EINVAL,
+                    "MIRSHA_SUBMIT_DEDUP does not combine with expectations here: "
+                    "mirsha_submit_slices_expect_dedup");
+    if (flags & ~(mixed ? 0 : MIRSHA_SUBMIT_DEDUP)) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
+    return MIRSHA_OK;
+}
 
 // The argument checks of a mixed submission, and its plan (mirsha_expect_plan)
 // into the context's scratch.  Nothing is queued and no ticket is consumed.
-static int expect_validate(mirsha_ctx* c, const ExpectArgs& xa, uint32_t n, int flags) {
-    if (!xa.dedup) {  // the flags are the caller's
-        if (flags & MIRSHA_SUBMIT_DEDUP)
-            return fail(c, MIRSHA_EINVAL,
-                        "MIRSHA_SUBMIT_DEDUP does not combine with expectations here: "
-                        "mirsha_submit_slices_expect_dedup");
-        if (flags) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
-    }
+static int expect_validate(mirsha_ctx* c, const ExpectArgs& xa, uint32_t n) {
     if (!xa.n_mismatch_out) return fail(c, MIRSHA_EINVAL, "n_mismatch_out is NULL");
     if (xa.m && (!xa.expect_of || !xa.expected)) return fail(c, MIRSHA_EINVAL, "NULL argument");
     if (xa.m > n) return fail(c, MIRSHA_EINVAL, "%u expectations for %u requests", xa.m, n);
@@ -37,16 +79,6 @@ static int expect_validate(mirsha_ctx* c, const ExpectArgs& xa, uint32_t n, int 
     if (mirsha_expect_plan(xa.expect_of, xa.m, n, c->xp_has.data(), c->xp_base.data()) != MIRSHA_OK)
         return fail(c, MIRSHA_EINVAL, "expect_of must be strictly increasing with every index below %u", n);
     return MIRSHA_OK;
-}
-
-// Page-locked, 16-byte aligned caller rows a kernel on the context's device may
-// store into: their device address, else NULL.
-static uint8_t* kernel_rows(mirsha_ctx* c, uint8_t* out) {
-    if (!out || (reinterpret_cast<uintptr_t>(out) & 15u) || !kernel_writable_host(out, c->device)) return nullptr;
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, out, 0) == hipSuccess) return static_cast<uint8_t*>(dp);
-    (void)hipGetLastError();
-    return nullptr;
 }
 
 // Sizes the (free) slot's expectation staging, device block and verdict, and
@@ -108,84 +140,59 @@ static int expect_queue(mirsha_ctx* c, AsyncSlot& sl, const uint8_t* d_digests, 
     return MIRSHA_OK;
 }
 
-// The slot's page-locked digest rows, as the select kernel addresses them.
-static int slot_rows(mirsha_ctx* c, AsyncSlot& sl, uint8_t** rows) {
-    void* dp = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer(&dp, sl.dig.p, 0));
-    *rows = static_cast<uint8_t*>(dp);
-    return MIRSHA_OK;
+// What a hashing ticket of n requests owes at retirement: its rows, and with
+// expectations (`xa`) the verdict: the device's, or all zero when there was
+// nothing to compare (m == 0: no expect_stage ran, so the words are set here).
+static void owe(AsyncSlot& sl, SlotRows rows, uint8_t* out, uint32_t n, const ExpectArgs* xa) {
+    SlotRetire& r = sl.retire;
+    r.rows = rows;
+    r.out = out;
+    r.n = n;
+    if (!xa) return;
+    r.bits = xa->bits_out;
+    r.count = xa->n_mismatch_out;
+    r.verdict = xa->m ? SlotVerdict::kDevice : SlotVerdict::kAllZero;
+    if (!xa->m) sl.xp.words = (uint32_t)(((uint64_t)n + 63u) >> 6);
 }
 
-// A retired mixed submission: the kept rows (requests without an expectation,
-// and mismatches) from the slot's rows to the caller unless the kernel stored
-// them there itself, walking ~has | mis run by run; then the verdict.
-static void expect_complete(AsyncSlot& sl) {
-    ExpectSlot& x = sl.xp;
-    const uint32_t n = sl.n;
-    if (!x.select) {  // no expectation: every row is already the caller's, nothing differs
-        if (x.user_bits) memset(x.user_bits, 0, 8ull * x.words);
-        *x.user_count = 0;
-        return;
-    }
-    const uint64_t* has = x.stage.as<uint64_t>();
-    const uint8_t* v = x.verdict.as<uint8_t>();
-    const uint64_t* mis = reinterpret_cast<const uint64_t*>(v + 8);
-    if (!x.rows_direct) {
-        const uint8_t* d = sl.dig.as<uint8_t>();
-        uint64_t run0 = 0, run = 0;
-        auto flush = [&] {
-            if (run) memcpy(sl.user_out + 32ull * run0, d + 32ull * run0, 32ull * run);
-            run = 0;
-        };
-        for (uint32_t w = 0; w < x.words; w++) {
-            uint64_t keep = ~has[w] | mis[w];
-            if (w == x.words - 1 && (n & 63u)) keep &= (1ull << (n & 63u)) - 1ull;
-            uint32_t pos = 0;
-            while (pos < 64) {
-                const uint64_t rest = keep >> pos;
-                if (!rest) {
-                    flush();
-                    break;
-                }
-                const uint32_t z = (uint32_t)__builtin_ctzll(rest);
-                if (z) {
-                    flush();
-                    pos += z;
-                    continue;
-                }
-                const uint64_t inv = ~rest;
-                const uint32_t ones = inv ? (uint32_t)__builtin_ctzll(inv) : 64u;
-                if (!run) run0 = 64ull * w + pos;
-                run += ones;
-                pos += ones;
-                if (pos < 64) flush();  // the run ends inside this word
-            }
-        }
-        flush();
-    }
-    if (x.user_bits) memcpy(x.user_bits, mis, 8ull * x.words);
-    memcpy(x.user_count, v, sizeof(uint32_t));
-}
-
-// Copies a completed submission's digests to the caller, in origin order.
+// Retires a completed submission: its rows to the caller in origin order, then
+// its verdict (sl.retire says which of either).
 int async_complete(mirsha_ctx* c, AsyncSlot& sl) {
     HIP_TRY(c, hipEventSynchronize(sl.done));
     const auto t_done = Clock::now();
     sl.prof[MIRSHA_PROF_DEVICE] = std::chrono::duration<double, std::milli>(t_done - sl.t_queued).count();
+    const SlotRetire& r = sl.retire;
+    const ExpectSlot& x = sl.xp;
     const uint8_t* d = sl.dig.as<uint8_t>();
-    if (sl.cm.on) {
-        // commit submission: the values, unless the kernel stored them into values_out itself
-        if (!sl.cm.rows_direct && sl.cm.n_values) memcpy(sl.cm.user_values, sl.cm.rows.p, 32ull * sl.cm.n_values);
-    } else if (sl.xp.on && sl.xp.select) {
-        // mixed submission: only the kept rows are copied (expect_complete)
-    } else if (sl.direct) {
-        // mirsha_submit_batch into page-locked digests_out: already there
-    } else if (sl.rank.empty()) {
-        if (sl.n) memcpy(sl.user_out, d, 32ull * sl.n);
-    } else {
-        for (uint32_t i = 0; i < sl.n; i++) memcpy(sl.user_out + 32ull * i, d + 32ull * sl.rank[i], 32);
+    const uint8_t* v = x.verdict.as<uint8_t>();  // [count u32, pad | mismatch bitmap]
+    switch (r.rows) {
+    case SlotRows::kInPlace:
+        break;
+    case SlotRows::kCopyAll:
+        if (r.n) memcpy(r.out, d, 32ull * r.n);
+        break;
+    case SlotRows::kFanOut:
+        for (uint32_t i = 0; i < r.n; i++) memcpy(r.out + 32ull * i, d + 32ull * sl.rank[i], 32);
+        break;
+    case SlotRows::kKept:  // requests without an expectation, and mismatches
+        mirsha::host::copy_kept_rows(x.stage.as<uint64_t>(), reinterpret_cast<const uint64_t*>(v + 8), r.n, d, r.out);
+        break;
+    case SlotRows::kCommit:
+        if (r.n) memcpy(r.out, sl.cm.rows.p, 32ull * r.n);
+        break;
     }
-    if (sl.xp.on) expect_complete(sl);
+    switch (r.verdict) {
+    case SlotVerdict::kNone:
+        break;
+    case SlotVerdict::kAllZero:
+        if (r.bits) memset(r.bits, 0, 8ull * x.words);
+        *r.count = 0;
+        break;
+    case SlotVerdict::kDevice:
+        if (r.bits) memcpy(r.bits, v + 8, 8ull * x.words);
+        memcpy(r.count, v, sizeof(uint32_t));
+        break;
+    }
     sl.busy = false;
     c->done_ticket = std::max(c->done_ticket, sl.ticket);
     sl.prof[MIRSHA_PROF_SCATTER] = ms_since(t_done);
@@ -206,14 +213,13 @@ int async_wait_upto(mirsha_ctx* c, uint64_t ticket) {
 }
 
 int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
-                 const uint32_t* slice_first, uint32_t n, uint8_t* out, int flags, uint64_t* ticket_out,
+                 const uint32_t* slice_first, uint32_t n, uint8_t* out, bool want_dedup, uint64_t* ticket_out,
                  uint32_t* n_unique_out, const ExpectArgs* xa = nullptr) {
     auto t0 = Clock::now();
     if (xa)
-        if (int rc = expect_validate(c, *xa, n, flags)) return rc;
+        if (int rc = expect_validate(c, *xa, n)) return rc;
     // a deduplicated mixed cycle counts its expectation plan as validation
-    const double t_xplan = xa && xa->dedup ? ms_since(t0) : 0.0;
-    if (flags & ~MIRSHA_SUBMIT_DEDUP) return fail(c, MIRSHA_EINVAL, "unknown submit flags 0x%x", flags);
+    const double t_xplan = xa && want_dedup ? ms_since(t0) : 0.0;
     t0 = Clock::now();
     // Which requests reach the GPU: all, or one per distinct content.  With
     // dedup the requests are scanned in segments in origin order
@@ -224,7 +230,7 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     // byte for byte in the same walk, while its bytes are cache-warm.
     // Representatives found later (new contents of later segments, and
     // fingerprint collisions, rare) follow in one second launch.
-    const bool dedup = (flags & MIRSHA_SUBMIT_DEDUP) && n > 1;
+    const bool dedup = want_dedup && n > 1;
     double ph[MIRSHA_PROF_PHASES] = {};
     std::vector<uint32_t>& len = c->sl_len;  // context scratch (single caller), grow-only
     if (dedup) {
@@ -235,16 +241,11 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     }
     ph[MIRSHA_PROF_VALIDATE] = ms_since(t0) + t_xplan;
     t0 = Clock::now();
-    if (int rc = use_device(c)) return rc;
-    AsyncSlot& sl = c->slots[(c->next_ticket - 1) % kAsyncSlots];
-    if (sl.busy)
-        if (int rc = async_wait_upto(c, sl.ticket)) return rc;  // ring full: retire the oldest
-    sl.rank.clear();
-    sl.direct = false;
-    sl.xp.on = sl.xp.select = false;
-    sl.cm.on = false;
+    AsyncSlot* slot = nullptr;
+    if (int rc = ring_acquire(c, &slot)) return rc;
+    AsyncSlot& sl = *slot;
+    RingQueued queued(c->stream);
     HIP_TRY(c, sl.dig.ensure(32ull * std::max<uint32_t>(n, 1)));
-    if (!sl.done) HIP_TRY(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     // Mixed submission with expectations: the select kernel stands where the
     // digests' D2H copy stood, storing the kept rows into a page-locked
     // digests_out or else into the slot's page-locked rows.
@@ -256,12 +257,13 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     const bool gather = sel && dedup;
     const uint8_t* gather_dig[2] = {nullptr, nullptr};  // the launches' digest rows on the device
     uint8_t* sel_rows = nullptr;
+    SlotRows rows = SlotRows::kCopyAll;
     if (sel) {
         if (int rc = expect_stage(c, sl, *xa, n, gather)) return rc;
-        sel_rows = kernel_rows(c, out);
-        sl.xp.rows_direct = sel_rows != nullptr;
+        sel_rows = host_rows(c, out);
+        rows = sel_rows ? SlotRows::kInPlace : SlotRows::kKept;
         if (!sel_rows)
-            if (int rc = slot_rows(c, sl, &sel_rows)) return rc;
+            if (int rc = pinned_rows(c, sl.dig, &sel_rows)) return rc;
     }
     ph[MIRSHA_PROF_PLAN] = ms_since(t0);
     // Packs requests `ids` (identity when null) into `stage`, and queues their
@@ -295,6 +297,7 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
         const bool identity = bucket_order(plen, m, reinterpret_cast<uint32_t*>(st + o_ord));
         uint8_t* dv = dev.as<uint8_t>();
         if (m) {
+            queued.arm();
             HIP_TRY(c, hipMemcpyAsync(dv, st, o_end, hipMemcpyHostToDevice, c->stream));
             if (sel && !(gather && row0))
                 if (int rc = expect_h2d(c, sl, *xa, c->stream)) return rc;
@@ -325,17 +328,12 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
         mirsha::host::DedupScan d(slice_ptr, slice_len, slice_first, n, MIRSHA_MAX_MESSAGE_BYTES);
         const std::vector<uint32_t> seg = d.segments();
         std::vector<uint32_t> first_heads, later;  // the first launch's rows, then the second's
-        bool queued = false;
         for (size_t k = 0; k + 1 < seg.size(); k++) {
             const uint32_t lo = seg[k], hi = seg[k + 1];
             t0 = Clock::now();
             const bool ok = d.scan(lo, hi);
             ph[MIRSHA_PROF_VALIDATE] += ms_since(t0);
-            if (!ok) {
-                // the first launch still reads this slot's buffers: let it finish
-                if (queued) HIP_TRY(c, hipStreamSynchronize(c->stream));
-                return slice_errors(c, d.err(), n);
-            }
+            if (!ok) return slice_errors(c, d.err(), n);  // (a first launch already queued is drained: RingQueued)
             t0 = Clock::now();
             for (uint32_t i = lo; i < hi; i++) len[i] = (uint32_t)d.req_len()[i];
             d.assign(lo, hi, k == 0 ? first_heads : later);
@@ -343,7 +341,6 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
             if (k == 0) {
                 if (int rc = queue(first_heads.data(), (uint32_t)first_heads.size(), 0, sl.stage, sl.dev))
                     return rc;
-                queued = true;
                 sl.t_queued = Clock::now();
             }
             t0 = Clock::now();
@@ -362,18 +359,16 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
         if (gather) {
             row_of = reinterpret_cast<uint32_t*>(sl.xp.stage.as<uint8_t>() + sl.xp.o_row);
         } else {
-            sl.rank.resize(n);
+            if (sl.rank.size() < n) sl.rank.resize(n);
             row_of = sl.rank.data();
         }
         const bool identity = mirsha::host::dedup_rows(rep.data(), first_heads, later, n, row_of);
-        if (identity && !gather) sl.rank.clear();  // all distinct, rows already in origin order
         if (gather) {  // the kernel's loads stay inside the m rows
             uint32_t top = 0;
             for (uint32_t i = 0; i < n; i++) top = std::max(top, row_of[i]);
-            if (top >= m) {
-                HIP_TRY(c, hipStreamSynchronize(c->stream));  // the first launch reads this slot's buffers
-                return fail(c, MIRSHA_EHIP, "dedup: row %u of %u representatives", top, m);
-            }
+            if (top >= m) return fail(c, MIRSHA_EHIP, "dedup: row %u of %u representatives", top, m);
+        } else if (!identity) {  // (all distinct: the rows are in origin order already)
+            rows = SlotRows::kFanOut;
         }
         ph[MIRSHA_PROF_PLAN] += ms_since(t0);
         if (!later.empty())
@@ -388,23 +383,10 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
     }
     if (n_unique_out) *n_unique_out = m;
     HIP_TRY(c, hipEventRecord(sl.done, c->stream));
-    sl.busy = true;
-    sl.user_out = out;
-    sl.n = n;
-    sl.m = m;
-    if (xa) {
-        sl.xp.on = true;
-        sl.xp.select = sel;
-        sl.xp.words = (uint32_t)(((uint64_t)n + 63u) >> 6);
-        sl.xp.user_bits = xa->bits_out;
-        sl.xp.user_count = xa->n_mismatch_out;
-    }
-    sl.ticket = c->next_ticket++;
-    for (int k = 0; k < MIRSHA_PROF_PHASES; k++) sl.prof[k] = ph[k];
-    if (ticket_out) *ticket_out = sl.ticket;
+    owe(sl, rows, out, n, xa);
+    ring_publish(c, sl, queued, ph, ticket_out);
     return MIRSHA_OK;
 }
-
 
 // mirsha_submit_batch: n requests of a caller arena (request i =
 // arena[off[i], off[i] + len[i])), one slot of the ring.  The off / len
@@ -422,7 +404,7 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     auto t0 = Clock::now();
     const auto t_entry = t0;
     if (xa)
-        if (int rc = expect_validate(c, *xa, n, 0)) return rc;
+        if (int rc = expect_validate(c, *xa, n)) return rc;
     double ph[MIRSHA_PROF_PHASES] = {};
     // MIRSHA_SUBMIT_TRACE=1 (with MIRSHA_AB=1): a submission slower than 2 ms
     // prints where its time went (ms since entry at each step) on stderr.
@@ -458,11 +440,11 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     // Slot buffers: `stage2` = the metadata block [len u32 | order u32 | off
     // u64] (the device's copy has the same layout), `stage` = a copy of the
     // request bytes when they are not DMA'd from the caller, `dev` = [request
-    // bytes + slack | metadata | digests].
-    if (int rc = use_device(c)) return rc;
-    AsyncSlot& sl = c->slots[(c->next_ticket - 1) % kAsyncSlots];
-    if (sl.busy)
-        if (int rc = async_wait_upto(c, sl.ticket)) return rc;  // ring full: retire the oldest
+    // bytes + slack | metadata | digests].  The slot comes first: the pass
+    // below writes the metadata block into it.
+    AsyncSlot* slot = nullptr;
+    if (int rc = ring_acquire(c, &slot)) return rc;
+    AsyncSlot& sl = *slot;
     tr[0] = ms_since(t_entry);
     const uint64_t o_len = 0, o_ord = align8(4ull * n), o_off = align8(o_ord + 4ull * n), o_end = o_off + 8ull * n;
     HIP_TRY(c, sl.stage2.ensure(std::max<uint64_t>(o_end, 8)));
@@ -538,11 +520,8 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     ph[MIRSHA_PROF_VALIDATE] = ms_since(t0);
     tr[2] = ms_since(t_entry);
     t0 = Clock::now();
-    sl.rank.clear();
-    sl.xp.on = sl.xp.select = false;
-    sl.cm.on = false;
-    for (hipEvent_t* e : {&sl.done, &sl.ev_in, &sl.ev_kern})
-        if (!*e) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    for (hipEvent_t* e : {&sl.ev_in, &sl.ev_kern})
+        if (int rc = ensure_event(c, e)) return rc;
     // Request bytes in on xin, the kernel on the context stream; digests
     // stored by the kernel into a page-locked digests_out (metadata then on
     // xin too), else out on xout with the metadata on the kernel stream.
@@ -551,7 +530,7 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     if (!c->xin) HIP_TRY(c, hipStreamCreateWithFlags(&c->xin, hipStreamNonBlocking));
     if (!c->xout) HIP_TRY(c, hipStreamCreateWithFlags(&c->xout, hipStreamNonBlocking));
     const bool from_caller = dense && n && host_pinned(arena + lo);
-    sl.direct = host_pinned(out);
+    const bool direct = host_pinned(out);  // digests by DMA (or the kernel) straight into digests_out
     // A page-locked digests_out is written by the kernel itself (posted
     // writes over PCIe; visible when the kernel's completion is), and the
     // metadata follows the request bytes on xin: every SDMA copy of the
@@ -559,25 +538,19 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     // metadata, D2H) the runtime now and then blocked a hipMemcpyAsync for
     // 8-15 ms (profiles/r05w: 13-22 ms calls of the chunked HashBatch); with
     // one copy stream no call stalled, at the same steady-state speed.
-    uint8_t* kout = nullptr;
-    if (sl.direct && n && (reinterpret_cast<uintptr_t>(out) & 15u) == 0 && kernel_writable_host(out, c->device)) {
-        void* dp = nullptr;
-        if (hipHostGetDevicePointer(&dp, out, 0) == hipSuccess)
-            kout = static_cast<uint8_t*>(dp);
-        else
-            (void)hipGetLastError();
-    }
+    uint8_t* const kout = direct && n ? host_rows(c, out) : nullptr;
     // Mixed submission with expectations: the hashing kernel keeps its digests
     // on the device, and the select kernel behind it stores the kept rows into
     // a kernel-writable digests_out, else into the slot's page-locked rows.
     const bool sel = xa && xa->m;
     uint8_t* sel_rows = kout;
-    if (!sl.direct || (sel && !kout)) HIP_TRY(c, sl.dig.ensure(32ull * std::max<uint32_t>(n, 1)));
+    SlotRows rows = direct ? SlotRows::kInPlace : SlotRows::kCopyAll;
+    if (!direct || (sel && !kout)) HIP_TRY(c, sl.dig.ensure(32ull * std::max<uint32_t>(n, 1)));
     if (sel) {
         if (int rc = expect_stage(c, sl, *xa, n)) return rc;
-        sl.xp.rows_direct = kout != nullptr;
+        rows = kout ? SlotRows::kInPlace : SlotRows::kKept;
         if (!kout)
-            if (int rc = slot_rows(c, sl, &sel_rows)) return rc;
+            if (int rc = pinned_rows(c, sl.dig, &sel_rows)) return rc;
     }
     // device: [request bytes + slack | len u32 | order u32 | off u64 | digests]
     const uint64_t d_meta = align8(bytes + kArenaSlack);
@@ -594,7 +567,9 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     tr[3] = ms_since(t_entry);
     t0 = Clock::now();
     uint8_t* dv = sl.dev.as<uint8_t>();
+    RingQueued queued(c->xin, c->stream, c->xout);
     if (from_caller) {
+        queued.arm();
         HIP_TRY(c, hipMemcpyAsync(dv, arena + lo, bytes, hipMemcpyHostToDevice, c->xin));
     } else if (dense) {
         mirsha::host::pack_range(arena + lo, nullptr, nullptr, nullptr, 0, nullptr, 0, bytes, st,
@@ -613,11 +588,10 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
                            true);
     }
     tr[4] = ms_since(t_entry);
-    // Queue the copies and the kernel.  A failure part-way leaves work that
-    // reads this slot's buffers in flight while the slot is not marked busy:
-    // drain the three streams before reporting it.
+    // Queue the copies and the kernel (a failure part-way: RingQueued).
     auto queue = [&]() -> int {
         if (n) {
+            queued.arm();
             if (!from_caller && bytes) HIP_TRY(c, hipMemcpyAsync(dv, st, bytes, hipMemcpyHostToDevice, c->xin));
             // The metadata: behind the request bytes on xin when the kernel
             // stores the digests (one copy stream), else on the kernel stream.
@@ -660,7 +634,7 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
             HIP_TRY(c, hipEventRecord(sl.ev_kern, c->stream));
             HIP_TRY(c, hipStreamWaitEvent(c->xout, sl.ev_kern, 0));
             tq[5] = ms_since(t_entry);
-            HIP_TRY(c, hipMemcpyAsync(sl.direct ? out : sl.dig.as<uint8_t>(), dv + d_dig, 32ull * n,
+            HIP_TRY(c, hipMemcpyAsync(direct ? out : sl.dig.as<uint8_t>(), dv + d_dig, 32ull * n,
                                       hipMemcpyDeviceToHost, c->xout));
             tq[6] = ms_since(t_entry);
         }
@@ -668,28 +642,13 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
         tq[7] = ms_since(t_entry);
         return MIRSHA_OK;
     };
-    if (int rc = queue()) {
-        for (hipStream_t q : {c->xin, c->stream, c->xout}) (void)hipStreamSynchronize(q);
-        return rc;
-    }
+    if (int rc = queue()) return rc;
     sl.t_queued = Clock::now();
     ph[MIRSHA_PROF_PACK] = ms_since(t0);
     tr[5] = ms_since(t_entry);
     trace_done("arena");
-    sl.busy = true;
-    sl.user_out = out;
-    sl.n = n;
-    sl.m = n;
-    if (xa) {
-        sl.xp.on = true;
-        sl.xp.select = sel;
-        sl.xp.words = (uint32_t)(((uint64_t)n + 63u) >> 6);
-        sl.xp.user_bits = xa->bits_out;
-        sl.xp.user_count = xa->n_mismatch_out;
-    }
-    sl.ticket = c->next_ticket++;
-    for (int k = 0; k < MIRSHA_PROF_PHASES; k++) sl.prof[k] = ph[k];
-    *ticket_out = sl.ticket;
+    owe(sl, rows, out, n, xa);
+    ring_publish(c, sl, queued, ph, ticket_out);
     return MIRSHA_OK;
 }
 
@@ -703,7 +662,7 @@ int mirsha_hash_slices_dedup(mirsha_ctx* c, const uint8_t* const* slice_ptr, con
     if (n_unique_out) *n_unique_out = 0;
     if (n == 0) return MIRSHA_OK;
     uint64_t t = 0;
-    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, out, MIRSHA_SUBMIT_DEDUP, &t, n_unique_out))
+    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, out, true, &t, n_unique_out))
         return rc;
     return async_wait_upto(c, t);
 }
@@ -711,7 +670,9 @@ int mirsha_hash_slices_dedup(mirsha_ctx* c, const uint8_t* const* slice_ptr, con
 int mirsha_submit_slices(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
                          const uint32_t* slice_first, uint32_t n, uint8_t* out, int flags, uint64_t* ticket_out) {
     if (!c || !ticket_out) return MIRSHA_EINVAL;
-    return async_submit(c, slice_ptr, slice_len, slice_first, n, out, flags, ticket_out, nullptr);
+    if (int rc = check_submit_flags(c, flags, false)) return rc;
+    return async_submit(c, slice_ptr, slice_len, slice_first, n, out, (flags & MIRSHA_SUBMIT_DEDUP) != 0, ticket_out,
+                        nullptr);
 }
 
 int mirsha_submit_batch(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
@@ -726,8 +687,9 @@ int mirsha_submit_slices_expect(mirsha_ctx* c, const uint8_t* const* slice_ptr, 
                                 const uint8_t* expected, uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
                                 uint32_t* n_mismatch_out, int flags, uint64_t* ticket_out) {
     if (!c || !ticket_out) return MIRSHA_EINVAL;
+    if (int rc = check_submit_flags(c, flags, true)) return rc;
     const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
-    return async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, flags, ticket_out, nullptr, &xa);
+    return async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, false, ticket_out, nullptr, &xa);
 }
 
 int mirsha_submit_batch_expect(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
@@ -747,7 +709,7 @@ int mirsha_hash_slices_expect(mirsha_ctx* c, const uint8_t* const* slice_ptr, co
     if (!c) return MIRSHA_EINVAL;
     uint64_t t = 0;
     const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
-    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, 0, &t, nullptr, &xa)) return rc;
+    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, false, &t, nullptr, &xa)) return rc;
     return async_wait_upto(c, t);
 }
 
@@ -756,9 +718,8 @@ int mirsha_submit_slices_expect_dedup(mirsha_ctx* c, const uint8_t* const* slice
                                       const uint8_t* expected, uint32_t m, uint8_t* digests_out, uint64_t* bits_out,
                                       uint32_t* n_mismatch_out, uint32_t* n_unique_out, uint64_t* ticket_out) {
     if (!c || !ticket_out) return MIRSHA_EINVAL;
-    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out, true};
-    return async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, MIRSHA_SUBMIT_DEDUP, ticket_out,
-                        n_unique_out, &xa);
+    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
+    return async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, true, ticket_out, n_unique_out, &xa);
 }
 
 int mirsha_hash_slices_expect_dedup(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t* slice_len,
@@ -767,9 +728,8 @@ int mirsha_hash_slices_expect_dedup(mirsha_ctx* c, const uint8_t* const* slice_p
                                     uint32_t* n_mismatch_out, uint32_t* n_unique_out) {
     if (!c) return MIRSHA_EINVAL;
     uint64_t t = 0;
-    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out, true};
-    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, MIRSHA_SUBMIT_DEDUP, &t,
-                              n_unique_out, &xa))
+    const ExpectArgs xa{expect_of, expected, m, bits_out, n_mismatch_out};
+    if (int rc = async_submit(c, slice_ptr, slice_len, slice_first, n, digests_out, true, &t, n_unique_out, &xa))
         return rc;
     return async_wait_upto(c, t);
 }

@@ -210,8 +210,8 @@ uint32_t commit_seg_prio() {
 
 // Both forms of mirsha_chains_commit_submit.  Order: every check and the plan
 // (into the context's scratch; a failure leaves the ring as it was), then the
-// slot (retiring its previous ticket), the staging copy, and the device work
-// on the commit stream.
+// ring's slot lifecycle (mirsha_ctx.h): the slot, the staging copy, the device
+// work on the commit stream, the ticket.
 int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
                   const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
                   uint32_t* n_values_out, uint64_t* ticket_out) {
@@ -243,17 +243,17 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
     }
     ph[MIRSHA_PROF_VALIDATE] = ms_since(t0);
     t0 = Clock::now();
-    if (int rc = use_device(c)) return rc;
-    AsyncSlot& sl = c->slots[(c->next_ticket - 1) % kAsyncSlots];
-    if (sl.busy)
-        if (int rc = async_wait_upto(c, sl.ticket)) return rc;  // ring full: retire the oldest
+    AsyncSlot* slot = nullptr;
+    if (int rc = ring_acquire(c, &slot)) return rc;
+    AsyncSlot& sl = *slot;
     CommitSlot& cm = sl.cm;
-    if (!sl.done) HIP_TRY(c, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     if (ns) {
         if (!c->xcommit) HIP_TRY(c, hipStreamCreateWithFlags(&c->xcommit, hipStreamNonBlocking));
-        if (!ch->ev_commit) HIP_TRY(c, hipEventCreateWithFlags(&ch->ev_commit, hipEventDisableTiming));
-        if (on_device && !sl.ev_in) HIP_TRY(c, hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
+        if (int rc = ensure_event(c, &ch->ev_commit)) return rc;
+        if (on_device)
+            if (int rc = ensure_event(c, &sl.ev_in)) return rc;
     }
+    RingQueued queued(c->xcommit);
     // The slot's block: [seg_chain | sfirst | seg_flags | ent | pad to 16 | host table].
     const uint64_t o_first = 4ull * ns, o_flags = o_first + 4ull * (ns + 1u), o_ent = o_flags + 4ull * ns;
     const uint64_t o_tab = align16(o_ent + 4ull * entries);
@@ -262,7 +262,6 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
     // FIRST lanes read a copy of the states taken ahead of the launch.
     bool straddle = false;
     uint8_t* rows = nullptr;
-    bool rows_direct = false;
     if (ns) {
         const uint32_t* plan = c->cm_plan.data();
         uint32_t first_wave = 0;
@@ -274,20 +273,15 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
         HIP_TRY(c, cm.dev.ensure(bytes));
         if (straddle) HIP_TRY(c, cm.snap.ensure(72ull * ch->n));
         if (values) {
-            // page-locked and 16-byte aligned: the kernel stores the values there itself
-            if (!(reinterpret_cast<uintptr_t>(values_out) & 15u) && kernel_writable_host(values_out, c->device)) {
-                void* dp = nullptr;
-                if (hipHostGetDevicePointer(&dp, values_out, 0) == hipSuccess)
-                    rows = static_cast<uint8_t*>(dp);
-                else
-                    (void)hipGetLastError();
-            }
-            rows_direct = rows != nullptr;
+            // a kernel-writable values_out receives the values from the kernel
+            // itself, else the slot's rows do, copied out at retirement
+            rows = host_rows(c, values_out);
             if (!rows) {
                 HIP_TRY(c, cm.rows.ensure(32ull * values));
-                void* dp = nullptr;
-                HIP_TRY(c, hipHostGetDevicePointer(&dp, cm.rows.p, 0));
-                rows = static_cast<uint8_t*>(dp);
+                if (int rc = pinned_rows(c, cm.rows, &rows)) return rc;
+                sl.retire.rows = SlotRows::kCommit;
+                sl.retire.out = values_out;
+                sl.retire.n = values;
             }
         }
     }
@@ -302,6 +296,7 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
         memcpy(st + o_ent, plan + o_pent, 4ull * entries);
         if (!on_device && n_digests) memcpy(st + o_tab, digests, 32ull * n_digests);
         hipStream_t q = c->xcommit;
+        queued.arm();
         if (on_device) {  // the table is read behind whatever was queued on the context's stream
             HIP_TRY(c, hipEventRecord(sl.ev_in, c->stream));
             HIP_TRY(c, hipStreamWaitEvent(q, sl.ev_in, 0));
@@ -337,28 +332,13 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
         return MIRSHA_OK;
     };
     if (ns) {
-        if (int rc = queue()) {
-            (void)hipStreamSynchronize(c->xcommit);  // what was queued reads this slot's buffers
-            return rc;
-        }
+        if (int rc = queue()) return rc;  // (what it queued is drained: RingQueued)
         ch->commit_queued = true;
     }
     sl.t_queued = Clock::now();
     ph[MIRSHA_PROF_PACK] = ms_since(t0);
-    sl.rank.clear();
-    sl.direct = false;
-    sl.xp.on = sl.xp.select = false;
-    cm.on = true;
-    cm.rows_direct = rows_direct;
-    cm.n_values = ns ? values : 0u;
-    cm.user_values = values_out;
-    sl.busy = true;
-    sl.user_out = nullptr;
-    sl.n = sl.m = 0;
-    sl.ticket = c->next_ticket++;
-    for (int k = 0; k < MIRSHA_PROF_PHASES; k++) sl.prof[k] = ph[k];
     *n_values_out = values;
-    *ticket_out = sl.ticket;
+    ring_publish(c, sl, queued, ph, ticket_out);
     return MIRSHA_OK;
 }
 

@@ -10,12 +10,19 @@
 //                       _digest_lists: compare on the device, verdict back)
 //   mirsha_plan.hip     request -> batch plans: sequential, fused (placement
 //                       probe), overlapped cycles (mirsha_pipeline_*)
-//   mirsha_async.hip    the asynchronous ring (mirsha_submit_* / wait / poll,
-//                       dedup, mixed hash-and-verify cycles: *_expect,
-//                       both in one ticket: *_expect_dedup)
+//   mirsha_async.hip    the asynchronous ring: the slot lifecycle every ticket
+//                       kind shares (ring_acquire -> stage / queue ->
+//                       ring_publish -> async_complete; RingQueued for a
+//                       submission that fails after it queued work) and the
+//                       hashing tickets (mirsha_submit_* / wait / poll, dedup,
+//                       mixed hash-and-verify cycles: *_expect, both in one
+//                       ticket: *_expect_dedup)
 //   mirsha_expect.hip   the select kernels of the mixed submissions
-//   mirsha_commit_ring.hip  a cycle's Commits on the ring
+//   mirsha_commit_ring.hip  a cycle's Commits as a ticket of that ring
 //                       (mirsha_chains_commit_submit*) and their segment kernel
+//   mirsha_host.cpp     host-only logic, no HIP (dedup scan, packing, the
+//                       expectation / commit plans, a mixed ticket's kept-rows
+//                       walk): unit-tested on the CPU (tests/c)
 //   mirsha_multi.hip    the multi-device drop-in (mirsha_multi_*)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
@@ -153,14 +160,9 @@ inline double ms_since(Clock::time_point t0) {
 
 // The expectation side of a mixed submission (mirsha_submit_*_expect).
 struct ExpectSlot {
-    bool on = false;      // the ticket owes a verdict (bits_out / n_mismatch_out)
-    bool select = false;  // expect_select_kernel ran (m > 0): only the kept rows are the caller's
-    bool rows_direct = false;  // the kernel stored the kept rows into digests_out itself
     uint32_t words = 0;   // ceil(n / 64)
     uint64_t o_exp = 0, o_ver = 0, h2d = 0;  // offsets of the expected rows and the verdict; bytes of `stage`
     uint64_t o_row = 0;  // offset of row_of u32[n] (a deduplicated mixed submission), behind the expected rows
-    uint64_t* user_bits = nullptr;
-    uint32_t* user_count = nullptr;
     PinnedBuf stage;    // [has u64[words] | base u32[words], padded to 16 | expected 32 m | row_of]: H2D source
     PinnedBuf verdict;  // [count u32, pad | mismatch bitmap u64[words]]: D2H target
     DevBuf dev;         // stage's layout, then the verdict's (16-byte aligned)
@@ -170,14 +172,34 @@ struct ExpectSlot {
 // copies of everything the device reads, so the caller's arrays are free when
 // the call returns.
 struct CommitSlot {
-    bool on = false;           // the ticket is a commit programme
-    bool rows_direct = false;  // the kernel stored the values into values_out itself
-    uint32_t n_values = 0;
-    uint8_t* user_values = nullptr;
     PinnedBuf stage;  // [seg_chain | sfirst | seg_flags | ent | pad to 16 | host digest table]: ONE H2D
     DevBuf dev;       // the same layout
     DevBuf snap;      // [h | pend | cnt] as the launch found them (see commit_submit)
     PinnedBuf rows;   // the values' rows when values_out is not kernel-writable
+};
+
+// What a ticket owes its caller when it retires (async_complete): how its rows
+// reach `out`, and which verdict goes to `bits` / `count`.  ring_acquire resets
+// it, the submitter fills it in before ring_publish.
+enum class SlotRows : uint8_t {
+    kInPlace,  // already there: a kernel or a DMA wrote the caller's memory
+    kCopyAll,  // rows [0, n) of the slot's `dig`
+    kFanOut,   // row rank[i] of `dig` for request i (dedup)
+    kKept,     // a mixed ticket's kept rows, from `dig` (mirsha::host::copy_kept_rows)
+    kCommit,   // n checkpoint values from cm.rows
+};
+enum class SlotVerdict : uint8_t {
+    kNone,
+    kAllZero,  // a mixed ticket without expectations (m == 0): nothing differs
+    kDevice,   // count and bitmap from xp.verdict
+};
+struct SlotRetire {
+    SlotRows rows = SlotRows::kInPlace;
+    SlotVerdict verdict = SlotVerdict::kNone;
+    uint8_t* out = nullptr;  // digests_out / values_out
+    uint32_t n = 0;          // its rows: requests, or checkpoint values
+    uint64_t* bits = nullptr;  // bits_out (may be NULL) and n_mismatch_out of a ticket that owes a verdict
+    uint32_t* count = nullptr;
 };
 
 struct AsyncSlot {
@@ -191,10 +213,8 @@ struct AsyncSlot {
     hipEvent_t ev_in = nullptr, ev_kern = nullptr;  // arena submissions: H2D landed, kernel done
     uint64_t ticket = 0;
     bool busy = false;
-    uint8_t* user_out = nullptr;
-    bool direct = false;  // digests DMA'd straight into a page-locked user_out (nothing to copy at retire)
-    uint32_t n = 0, m = 0;
-    std::vector<uint32_t> rank;  // request -> row of `dig` (empty: identity)
+    SlotRetire retire;
+    std::vector<uint32_t> rank;  // request -> row of `dig` (SlotRows::kFanOut; grow-only)
     double prof[MIRSHA_PROF_PHASES] = {};  // this submission's host phases (published when it completes)
     ExpectSlot xp;
     CommitSlot cm;
@@ -449,6 +469,43 @@ int slice_lengths(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t
 // ---- mirsha_async.hip
 // Retires every submission up to `ticket`, in ticket order.
 int async_wait_upto(mirsha_ctx* c, uint64_t ticket);
+
+// The life of a ring slot, the same for every kind of ticket ("The
+// ring"): ring_acquire -> the submitter stages, queues its device work with
+// sl.done behind it and fills sl.retire in -> ring_publish -> async_complete.
+// A submission that fails before ring_publish consumes no ticket; the device
+// work it had queued still reads the slot's buffers, so it is drained (RingQueued).
+
+// The slot the next ticket takes: makes the device current, retires the slot's
+// previous ticket if it is still busy, resets sl.retire, makes sure of sl.done.
+int ring_acquire(mirsha_ctx* c, AsyncSlot** slot);
+int ensure_event(mirsha_ctx* c, hipEvent_t* e);  // creates *e (no timing) unless it exists
+
+// The streams a submission queues device work on: arm() before the first
+// queued operation, ring_publish disarms; still armed at the end of the
+// submitter (every exit with an error), it synchronises them.
+struct RingQueued {
+    hipStream_t s[3];
+    bool armed = false;
+    explicit RingQueued(hipStream_t a, hipStream_t b = nullptr, hipStream_t c = nullptr) : s{a, b, c} {}
+    RingQueued(const RingQueued&) = delete;
+    ~RingQueued() {
+        for (hipStream_t q : s)
+            if (armed && q) (void)hipStreamSynchronize(q);
+    }
+    void arm() { armed = true; }
+};
+
+// The one place a ticket is handed out: the slot is busy with the next ticket,
+// keeps the submission's host phases ph[], and *ticket_out is written.
+void ring_publish(mirsha_ctx* c, AsyncSlot& sl, RingQueued& queued, const double* ph, uint64_t* ticket_out);
+
+// Caller memory a kernel on the context's device may store 128-bit rows into
+// (page-locked for that device or portable, 16-byte aligned): its device
+// alias, else NULL.
+uint8_t* host_rows(mirsha_ctx* c, void* p);
+// A slot's own page-locked rows, as a kernel addresses them.
+int pinned_rows(mirsha_ctx* c, const PinnedBuf& b, uint8_t** rows);
 
 // ---- mirsha_plan.hip
 int plan_build(mirsha_ctx* c, mirsha_pipeline* p, uint32_t n_req, const uint32_t* idx, const uint32_t* first,

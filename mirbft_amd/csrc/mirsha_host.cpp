@@ -581,6 +581,40 @@ bool dedup_rows(const uint32_t* rep, const std::vector<uint32_t>& heads0, const 
     return identity;
 }
 
+void copy_kept_rows(const uint64_t* has, const uint64_t* mis, uint32_t n, const uint8_t* src, uint8_t* dst) {
+    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) >> 6);
+    uint64_t run0 = 0, run = 0;  // the open run of kept rows: [run0, run0 + run)
+    auto flush = [&] {
+        if (run) memcpy(dst + 32ull * run0, src + 32ull * run0, 32ull * run);
+        run = 0;
+    };
+    for (uint32_t w = 0; w < words; w++) {
+        uint64_t keep = ~has[w] | mis[w];
+        if (w == words - 1 && (n & 63u)) keep &= (1ull << (n & 63u)) - 1ull;
+        uint32_t pos = 0;
+        while (pos < 64) {
+            const uint64_t rest = keep >> pos;
+            if (!rest) {
+                flush();
+                break;
+            }
+            const uint32_t z = (uint32_t)__builtin_ctzll(rest);
+            if (z) {
+                flush();
+                pos += z;
+                continue;
+            }
+            const uint64_t inv = ~rest;
+            const uint32_t ones = inv ? (uint32_t)__builtin_ctzll(inv) : 64u;
+            if (!run) run0 = 64ull * w + pos;
+            run += ones;
+            pos += ones;
+            if (pos < 64) flush();  // the run ends inside this word
+        }
+    }
+    flush();
+}
+
 namespace {
 // memcpy whose body bypasses the CPU caches (16-byte non-temporal stores):
 // page-locked staging written this way DMAs at the link's 57.4 GB/s, written

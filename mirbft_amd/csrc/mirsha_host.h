@@ -120,6 +120,12 @@ uint32_t dedup_plan(const uint8_t* const* ptr, const uint64_t* len, const uint32
 bool dedup_rows(const uint32_t* rep, const std::vector<uint32_t>& heads0, const std::vector<uint32_t>& later,
                 uint32_t n, uint32_t* row);
 
+// A retired mixed submission's kept rows (requests without an expectation,
+// and mismatches): copies the 32-byte row i of src to row i of dst for every
+// i < n with bit i of ~has | mis set (ceil(n / 64) words each; bits at and
+// above n are ignored), one memcpy per run of kept rows, across words too.
+void copy_kept_rows(const uint64_t* has, const uint64_t* mis, uint32_t n, const uint8_t* src, uint8_t* dst);
+
 // Copies request which[k] (k < m) to dst + dst_off[k], in parallel.  With
 // `stream` the stores bypass the CPU caches (non-temporal, fenced before
 // return): for page-locked staging a DMA reads next, which then runs at the

@@ -1,15 +1,19 @@
-// expect_unit.cpp -- CPU unit test of mirsha_expect_plan
+// expect_unit.cpp -- CPU unit test of mirsha_expect_plan and
+// mirsha::host::copy_kept_rows
 // (mirbft_amd/csrc/mirsha_host.cpp, compiled here with g++: no HIP, no GPU):
 // the bitmap and the per-word row bases of a mixed submission's expectations
 // against a bit-by-bit restatement, guard entries behind both outputs, and
-// the rejected index lists.  Prints "expect unit ok"; exit 1 with a message at
+// the rejected index lists; the kept-rows walk of a retired mixed ticket
+// against a row-by-row loop.  Prints "expect unit ok"; exit 1 with a message at
 // the first mismatch.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
 #include "mirsha.h"
+#include "mirsha_host.h"
 
 static int fails = 0;
 #define EXPECT(cond, ...)                                        \
@@ -60,7 +64,78 @@ static void reject(const std::vector<uint32_t>& of, uint32_t n, const char* what
     EXPECT(has[words] == kGuard64 && base[words] == kGuard32, "%s: wrote past its outputs", what);
 }
 
+// mirsha::host::copy_kept_rows against a one-row-at-a-time loop.  Row i of src
+// is filled with the byte i; dst holds exactly 32 n bytes (an overrun is the
+// sanitizer's to see), pre-filled with a guard byte no row below 0xA5 equals,
+// so both "row copied" and "row left alone" are checked for every i.
+static const uint8_t kGuard8 = 0xA5;
+
+static void kept(std::vector<uint64_t> has, std::vector<uint64_t> mis, uint32_t n, const char* what) {
+    const uint32_t words = (uint32_t)(((uint64_t)n + 63u) >> 6);
+    has.resize(words);
+    mis.resize(words);
+    uint8_t* src = (uint8_t*)malloc(32ull * n + 1);  // (+1: no zero-sized allocation)
+    uint8_t* dst = (uint8_t*)malloc(32ull * n);
+    for (uint32_t i = 0; i < n; i++) memset(src + 32ull * i, (int)i, 32);
+    if (n) memset(dst, kGuard8, 32ull * n);
+    mirsha::host::copy_kept_rows(has.data(), mis.data(), n, src, dst);
+    uint32_t bad = n;
+    for (uint32_t i = n; i-- > 0;) {
+        const bool keep = ((~has[i >> 6] | mis[i >> 6]) >> (i & 63u)) & 1u;
+        for (uint32_t b = 0; b < 32; b++)
+            if (dst[32ull * i + b] != (keep ? (uint8_t)i : kGuard8)) bad = i;
+    }
+    EXPECT(bad == n, "copy_kept_rows %s n=%u: row %u", what, n, bad);
+    free(src);
+    free(dst);
+}
+
+// Bits [lo, hi] kept (has clear), every other one not (has set, no mismatch).
+static std::vector<uint64_t> has_but(uint32_t lo, uint32_t hi) {
+    std::vector<uint64_t> has(3, ~0ull);
+    for (uint32_t i = lo; i <= hi; i++) has[i >> 6] &= ~(1ull << (i & 63u));
+    return has;
+}
+
+static void kept_rows_cases() {
+    std::mt19937_64 rng(11);
+    const std::vector<uint64_t> none(3, 0ull), all(3, ~0ull), alt(3, 0x5555555555555555ull);
+    for (uint32_t n : {0u, 1u, 63u, 64u, 65u, 127u, 128u, 130u}) {  // (no row byte reaches the guard's 0xA5)
+        kept(all, none, n, "nothing kept");
+        kept(none, none, n, "everything kept (no expectation)");
+        kept(all, all, n, "everything kept (every expectation wrong)");
+        kept(alt, none, n, "alternating");
+        kept(all, alt, n, "alternating mismatches");
+        kept(has_but(60, 70), none, n, "a run from 60 to 70");
+        kept(has_but(50, 63), none, n, "a run ending at 63");
+        kept(has_but(64, 80), none, n, "a run starting at 64");
+        kept(has_but(0, 129), none, n, "one run over every word");
+        if (n) kept(has_but(n - 1, n - 1), none, n, "only the last row");
+        if (n & 63u) {  // garbage at and above bit n of the last word is ignored
+            const uint32_t w = n >> 6;
+            const uint64_t above = ~0ull << (n & 63u);
+            std::vector<uint64_t> has = all, mis = none;
+            mis[w] |= above;
+            kept(has, mis, n, "mismatch garbage above n");
+            has[w] &= ~above;
+            kept(has, none, n, "has clear above n");
+            has = has_but(n - 1, n - 1);
+            has[w] &= ~above;
+            kept(has, mis, n, "the last row and garbage above n");
+        }
+        for (int k = 0; k < 200; k++) {
+            std::vector<uint64_t> has(3), mis(3);
+            for (int w = 0; w < 3; w++) {
+                has[w] = rng() | (k % 3 ? rng() : 0ull);  // denser expectations: longer gaps between kept runs
+                mis[w] = rng() & rng() & (k % 2 ? rng() : ~0ull);
+            }
+            kept(has, mis, n, "random");
+        }
+    }
+}
+
 int main() {
+    kept_rows_cases();
     std::mt19937_64 rng(7);
     for (uint32_t n : {0u, 1u, 63u, 64u, 65u, 128u, 1000u, 100003u, 600011u}) {  // the last: the parallel pass
         std::vector<uint32_t> full, alt, half;
