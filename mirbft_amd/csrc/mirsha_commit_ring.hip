@@ -2,77 +2,15 @@
 // (mirsha_chains_commit_submit / _submit_device, include/mirsha.h): the
 // commit stage of ProcessorWorkPool (commitInParallel, processor.go:363-394,
 // :447-470) beside its hash stage (mirsha_async.hip).  A translation unit of
-// its own, as mirsha_expect.hip: the hashing kernels' sources and code object
-// are untouched, and the synchronous mirsha_chains_commit keeps its kernel.
-#include <hip/hip_ext.h>
-
+// its own, as mirsha_expect.hip: the hashing kernels keep their code object,
+// and the synchronous mirsha_chains_commit keeps its kernel.  Both commit
+// kernels walk a programme by the same step (CommitStep / commit_fetch,
+// mirsha_device.h).
 #include "mirsha_ctx.h"
 
 namespace mirsha {
 
 namespace {
-
-// One step of a lane's programme; the step structure is chains_commit_kernel's
-// (mirsha_kernels.hip): at most one compression, i.e. two whole digests (the
-// first may be the pending one), or a checkpoint's single final block, or a
-// lone last write that becomes the pending digest without a compression.
-// Restated here, not shared: that file is no header, and neither its text nor
-// its code object may change (bench.py's traffic_key hashes it).
-struct SegStep {
-    uint4 a0, a1, b0, b1;  // raw rows of the two halves (zeros where the step loads none)
-    uint64_t bits;         // checkpoint: the message's bit length
-    uint32_t row;          // checkpoint: output row
-    bool use_pend;         // first half = the pending digest
-    bool have_a;           // checkpoint: a first half precedes the 0x80
-    bool write, cp;        // compress two digests / the final block (neither: nothing to hash)
-    bool keep;             // a lone last write: the first half becomes the pending digest
-};
-
-// Plans the step of a lane at entry e (x0 = ent[e], xn = ent[e + 1], each
-// loaded only below `end`), requests its digest rows, moves e and the digest
-// count n past it and loads the entries of the step after it.  Which entries
-// a step consumes depends on the entry kinds and the parity only, never on a
-// hash value, so this walk runs one step ahead of the hashing.  Every load is
-// guarded by the lane's own sfirst range: past `end` lie the next segment's
-// entries or the end of the array.
-__device__ __forceinline__ SegStep seg_fetch(const uint8_t* __restrict__ digests, const uint32_t* __restrict__ ent,
-                                             uint32_t end, uint32_t& e, uint64_t& n, uint32_t& x0, uint32_t& xn) {
-    SegStep s;
-    const bool live = e < end;
-    const bool odd = (n & 1u) != 0u;
-    const bool take0 = live && !odd && !(x0 & kCommitEntryCheckpoint);  // first half from the table
-    const uint32_t e1 = e + (take0 ? 1u : 0u);
-    const bool live1 = live && e1 < end;  // odd && live: e1 == e, so live1
-    const uint32_t x1 = take0 ? xn : x0;
-    s.write = live1 && !(x1 & kCommitEntryCheckpoint);
-    s.cp = live1 && (x1 & kCommitEntryCheckpoint) != 0u;
-    s.use_pend = odd && live1;
-    s.have_a = odd || take0;
-    s.keep = take0 && !live1;
-    s.row = x1 & ~kCommitEntryCheckpoint;
-    s.bits = (n + (take0 ? 1u : 0u)) * 256u;
-    s.a0 = s.a1 = s.b0 = s.b1 = make_uint4(0u, 0u, 0u, 0u);
-    if (take0) {
-        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x0);
-        s.a0 = d[0];
-        s.a1 = d[1];
-    }
-    if (s.write) {
-        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x1);
-        s.b0 = d[0];
-        s.b1 = d[1];
-    }
-    n = s.cp ? 0u : n + (take0 ? 1u : 0u) + (s.write ? 1u : 0u);
-    e = e1 + (live1 ? 1u : 0u);
-    x0 = e < end ? ent[e] : 0u;
-    xn = e + 1u < end ? ent[e + 1u] : 0u;  // e <= end <= 2^31: no wrap
-    return s;
-}
-
-__device__ __forceinline__ void seg_be_words(const uint4& v, uint32_t w[4]) {
-    w[0] = __builtin_bswap32(v.x); w[1] = __builtin_bswap32(v.y);
-    w[2] = __builtin_bswap32(v.z); w[3] = __builtin_bswap32(v.w);
-}
 
 // The wave's issue priority, once at entry.  The priority is wave-uniform;
 // readfirstlane keeps the branches scalar, so exactly one s_setprio executes
@@ -131,13 +69,13 @@ __global__ __launch_bounds__(kBlockThreads) void chains_commit_seg_kernel(
     }
     uint32_t x0 = e < end ? ent[e] : 0u;
     uint32_t xn = e + 1u < end ? ent[e + 1u] : 0u;
-    SegStep s = seg_fetch(digests, ent, end, e, n, x0, xn);
+    CommitStep s = commit_fetch(digests, ent, end, e, n, x0, xn);
     // Wave-uniform: a lane whose step does nothing has reached its end (only a
     // programme's last step can be without a compression).
     while (__ballot(s.write || s.cp || s.keep) != 0ull) {
-        const SegStep nx = seg_fetch(digests, ent, end, e, n, x0, xn);
+        const CommitStep nx = commit_fetch(digests, ent, end, e, n, x0, xn);
         uint32_t w[16];
-        seg_be_words(s.a0, w); seg_be_words(s.a1, w + 4); seg_be_words(s.b0, w + 8); seg_be_words(s.b1, w + 12);
+        be_words(s.a0, w); be_words(s.a1, w + 4); be_words(s.b0, w + 8); be_words(s.b1, w + 12);
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             if (s.use_pend) w[i] = pw[i];
@@ -170,26 +108,14 @@ __global__ __launch_bounds__(kBlockThreads) void chains_commit_seg_kernel(
     }
 }
 
-// Launched as every kernel of the library is (launch_k, mirsha_kernels.hip):
-// with the thread's pending timing events bound to the dispatch when a timed
-// launch set them.
 hipError_t launch_chains_commit_seg(const uint8_t* digests, const uint32_t* ent, const uint32_t* seg_chain,
                                     const uint32_t* sfirst, const uint32_t* seg_flags, uint32_t n_seg,
                                     const uint32_t* h_in, const uint32_t* pend_in, const uint64_t* cnt_in, uint32_t* h,
                                     uint32_t* pend, uint64_t* cnt, uint8_t* out, uint32_t prio, hipStream_t s) {
     if (n_seg == 0) return hipSuccess;
     const uint32_t grid = (n_seg + kBlockThreads - 1u) / kBlockThreads;
-    uint4* o = reinterpret_cast<uint4*>(out);
-    LaunchEvents& ev = next_launch_events();
-    if (ev.start && ev.stop) {
-        const hipEvent_t e0 = ev.start, e1 = ev.stop;
-        ev = LaunchEvents{};
-        hipExtLaunchKernelGGL(chains_commit_seg_kernel, dim3(grid), dim3(kBlockThreads), 0, s, e0, e1, 0u, digests, ent,
-                              seg_chain, sfirst, seg_flags, n_seg, h_in, pend_in, cnt_in, h, pend, cnt, o, prio);
-    } else {
-        chains_commit_seg_kernel<<<grid, kBlockThreads, 0, s>>>(digests, ent, seg_chain, sfirst, seg_flags, n_seg, h_in,
-                                                                pend_in, cnt_in, h, pend, cnt, o, prio);
-    }
+    launch_k(chains_commit_seg_kernel, grid, kBlockThreads, 0, s, digests, ent, seg_chain, sfirst, seg_flags, n_seg, h_in,
+             pend_in, cnt_in, h, pend, cnt, reinterpret_cast<uint4*>(out), prio);
     return hipGetLastError();
 }
 

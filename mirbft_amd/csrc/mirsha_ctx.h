@@ -47,8 +47,7 @@
 
 #include "../../include/mirsha.h"
 #include "mirsha_host.h"
-#include "mirsha_kernels.h"
-#include "sha256_device.h"
+#include "mirsha_device.h"
 
 namespace mirsha {
 // mirsha_expect.hip.  Mixed cycles (mirsha_submit_*_expect): compares the
@@ -330,7 +329,7 @@ struct mirsha_pipeline {
     std::vector<uint32_t> cidx, cfirst;      // compacted lists (no null entries)
     uint32_t uniform = 0;                    // B: identity lists of B entries (uniform_lists), else 0
     std::vector<uint32_t> order;             // request processing order
-    DevBuf d_cidx, d_cfirst, d_order, d_state;
+    DevBuf d_cidx, d_cfirst, d_order;
 };
 
 namespace mirsha_api {

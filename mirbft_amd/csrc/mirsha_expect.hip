@@ -2,8 +2,6 @@
 // submissions (mirsha_submit_*_expect and, deduplicated,
 // mirsha_submit_slices_expect_dedup; mirsha_async.hip).  A translation unit
 // of its own: the hashing kernels' sources and code object are untouched.
-#include <hip/hip_ext.h>
-
 #include "mirsha_ctx.h"
 
 namespace mirsha {
@@ -56,9 +54,6 @@ __global__ __launch_bounds__(kBlockThreads) void expect_select_kernel(const uint
     }
 }
 
-// Launched as every kernel of the library is (launch_k, mirsha_kernels.hip):
-// with the thread's pending timing events bound to the dispatch when a timed
-// launch set them.
 hipError_t launch_expect_select(const uint8_t* digests, const uint8_t* expected, const uint64_t* has,
                                 const uint32_t* base, uint32_t n, uint8_t* out, uint64_t* bits, uint32_t* count,
                                 hipStream_t s) {
@@ -69,15 +64,7 @@ hipError_t launch_expect_select(const uint8_t* digests, const uint8_t* expected,
     const unsigned long long* h = reinterpret_cast<const unsigned long long*>(has);
     uint4* o = reinterpret_cast<uint4*>(out);
     unsigned long long* b = reinterpret_cast<unsigned long long*>(bits);
-    LaunchEvents& ev = next_launch_events();
-    if (ev.start && ev.stop) {
-        const hipEvent_t e0 = ev.start, e1 = ev.stop;
-        ev = LaunchEvents{};
-        hipExtLaunchKernelGGL(expect_select_kernel, dim3(grid), dim3(kBlockThreads), 0, s, e0, e1, 0u, d, e, h, base, n,
-                              o, b, count);
-    } else {
-        expect_select_kernel<<<grid, kBlockThreads, 0, s>>>(d, e, h, base, n, o, b, count);
-    }
+    launch_k(expect_select_kernel, grid, kBlockThreads, 0, s, d, e, h, base, n, o, b, count);
     return hipGetLastError();
 }
 
@@ -138,15 +125,7 @@ hipError_t launch_expect_select_gather(const uint8_t* digests0, const uint8_t* d
     const unsigned long long* h = reinterpret_cast<const unsigned long long*>(has);
     uint4* o = reinterpret_cast<uint4*>(out);
     unsigned long long* b = reinterpret_cast<unsigned long long*>(bits);
-    LaunchEvents& ev = next_launch_events();
-    if (ev.start && ev.stop) {
-        const hipEvent_t e0 = ev.start, e1 = ev.stop;
-        ev = LaunchEvents{};
-        hipExtLaunchKernelGGL(expect_select_gather_kernel, dim3(grid), dim3(kBlockThreads), 0, s, e0, e1, 0u, d0, d1,
-                              m0, row_of, e, h, base, n, o, b, count);
-    } else {
-        expect_select_gather_kernel<<<grid, kBlockThreads, 0, s>>>(d0, d1, m0, row_of, e, h, base, n, o, b, count);
-    }
+    launch_k(expect_select_gather_kernel, grid, kBlockThreads, 0, s, d0, d1, m0, row_of, e, h, base, n, o, b, count);
     return hipGetLastError();
 }
 

@@ -87,10 +87,9 @@ constexpr uint32_t kMaxListDigests = (1u << 27) - 1u;
 constexpr uint32_t kMaxListEntries = (1u << 30) - 1u;
 hipError_t launch_lists(const uint8_t* digests, uint32_t n_digests, const uint32_t* idx, uint32_t n_entries,
                         const uint32_t* first, uint32_t n_lists, uint32_t* scratch, uint8_t* out, hipStream_t s);
-// One segment [ob, oe) of every (compacted) list chain; oe = kOpenEnd finalises all.
+// Every (compacted) list's whole chain, one lane per list.
 // uniform = B > 0: the lists are identity lists of B entries (list k =
 // entries [k B, min(k B + B, n_entries)), cidx[e] == e); cidx / cfirst unread.
-constexpr uint32_t kOpenEnd = 0xFFFFFFFEu;
 // K[j] + W[j] of a padding-only final block (0x80, zeros, the 64-bit bit
 // length of a message of L bytes, L a multiple of 64): its whole message
 // schedule is a constant (pad_block_kw, host side).
@@ -100,8 +99,7 @@ struct PadBlockKW {
 };
 PadBlockKW pad_block_kw(uint64_t L);
 hipError_t launch_chain(const uint8_t* digests, uint32_t n_digests, const uint32_t* cidx, uint32_t n_entries,
-                        const uint32_t* cfirst, uint32_t n_lists, uint32_t ob, uint32_t oe, uint32_t* state,
-                        uint8_t* out, hipStream_t s, uint32_t uniform = 0);
+                        const uint32_t* cfirst, uint32_t n_lists, uint8_t* out, hipStream_t s, uint32_t uniform = 0);
 // Whole (compacted) list chains by producer/consumer pairs, one 128-thread
 // workgroup per 64 lists; for at most kPairMaxGroups groups.
 hipError_t launch_chain_pair(const uint8_t* digests, uint32_t n_digests, const uint32_t* cidx, uint32_t n_entries,

@@ -20,11 +20,9 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstdio>
+#include <type_traits>
 
-#include <hip/hip_ext.h>
-
-#include "mirsha_kernels.h"
-#include "sha256_device.h"
+#include "mirsha_device.h"
 
 namespace mirsha {
 
@@ -934,9 +932,6 @@ __global__ __launch_bounds__(1024, 1) void sha256_msgs_cu_kernel(const uint8_t* 
 // 3 - floor(4 b / blocks): a chain is ~2x a request tile's length, so it keeps
 // up with the tiles' progress priorities instead of starving behind the second
 // generation.
-__device__ __forceinline__ uint32_t ld_u32(__amdgpu_buffer_rsrc_t rs, uint32_t off, bool live);
-__device__ __forceinline__ void load_digest(__amdgpu_buffer_rsrc_t rsrc, uint32_t id, bool live, uint4& x0,
-                                            uint4& x1);
 __device__ __forceinline__ void overlap_chain(const uint8_t* __restrict__ digests, uint32_t n_digests,
                                               const uint32_t* __restrict__ cidx, uint32_t n_entries,
                                               const uint32_t* __restrict__ cfirst, uint32_t n_lists,
@@ -952,16 +947,15 @@ __device__ __forceinline__ void overlap_chain(const uint8_t* __restrict__ digest
     const uint32_t L = 32u * c;
     const uint32_t nb = valid ? blocks_for_len(L) : 0u;
     const uint32_t wave_nb = blocks_for_len(32u * wave_max(c));
-    const __amdgpu_buffer_rsrc_t drs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)digests, (short)0, (int)(32u * n_digests), 0x00020000);
-    const __amdgpu_buffer_rsrc_t irs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)cidx, (short)0, (int)(4u * n_entries), 0x00020000);
+    const __amdgpu_buffer_rsrc_t drs = buffer_rsrc(digests, 32u * n_digests);
+    const __amdgpu_buffer_rsrc_t irs = buffer_rsrc(cidx, 4u * n_entries);
     uint32_t st[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) st[i] = kH0[i];
-    // Indices one block ahead; the block's digests are loaded right before its
-    // rounds (the other waves of the SIMD cover the latency; a digest prefetch
-    // would cost 16 VGPRs of the 8-wave budget).
+    // A load schedule of its own, not ListBlocks': indices one block ahead; the
+    // block's digests are loaded right before its rounds (the other waves of
+    // the SIMD cover the latency; a digest prefetch would cost 16 VGPRs of the
+    // 8-wave budget of 64).
     uint32_t i0 = ld_u32(irs, 4u * e0, 0u < c), i1 = ld_u32(irs, 4u * (e0 + 1u), 1u < c);
     for (uint32_t blk = 0; blk < wave_nb; blk++) {
         const uint32_t d0 = 2u * blk;
@@ -971,20 +965,8 @@ __device__ __forceinline__ void overlap_chain(const uint8_t* __restrict__ digest
         i0 = ld_u32(irs, 4u * (e0 + d0 + 2u), d0 + 2u < c);
         i1 = ld_u32(irs, 4u * (e0 + d0 + 3u), d0 + 3u < c);
         uint32_t w[16];
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            const uint32_t di = d0 + (uint32_t)half;
-            const uint4 a = x[2 * half], b = x[2 * half + 1];
-            w[8 * half + 0] = __builtin_bswap32(a.x) | (di == c ? 0x80000000u : 0u);
-            w[8 * half + 1] = __builtin_bswap32(a.y); w[8 * half + 2] = __builtin_bswap32(a.z);
-            w[8 * half + 3] = __builtin_bswap32(a.w); w[8 * half + 4] = __builtin_bswap32(b.x);
-            w[8 * half + 5] = __builtin_bswap32(b.y); w[8 * half + 6] = __builtin_bswap32(b.z);
-            w[8 * half + 7] = __builtin_bswap32(b.w);
-        }
-        if (blk + 1u == nb) {
-            w[14] = L >> 29;
-            w[15] = L << 3;
-        }
+        list_block_words(x, d0, c, w);
+        if (blk + 1u == nb) list_block_length(w, L);
         fixed_prio(prio_mode == 0u   ? 3u - min(3u, 4u * blk / wave_nb)
                    : prio_mode == 1u ? 3u - min(3u, blk)
                    : prio_mode == 2u ? 3u
@@ -1120,10 +1102,6 @@ __device__ __forceinline__ void consume_kw(uint4 (*slot)[64], uint32_t lane, uin
     }
 }
 
-__device__ __forceinline__ uint32_t ld_u32(__amdgpu_buffer_rsrc_t rs, uint32_t off, bool live);
-__device__ __forceinline__ void load_digest(__amdgpu_buffer_rsrc_t rsrc, uint32_t id, bool live, uint4& x0,
-                                            uint4& x1);
-
 // Producer-side sources of block words, called for blocks 0, 1, 2, ... in
 // order; each keeps the next block's loads in flight.
 struct ArenaBlocks {  // message bytes at any alignment in an arena (< 4 GiB)
@@ -1150,46 +1128,57 @@ struct ArenaBlocks {  // message bytes at any alignment in an arena (< 4 GiB)
     }
 };
 
-struct ListBlocks {  // concat(digests[cidx[e]]) of a compacted list (no null entries)
-    __amdgpu_buffer_rsrc_t drs, irs;
-    uint32_t e0, c, L, nb;
+// A lane's index policy: the digest index of ordinal o of its list.
+struct LoadedIndex {  // entries [e0, e0 + c) through the range-checked descriptor (0 for a dead slot)
+    __amdgpu_buffer_rsrc_t irs;
+    uint32_t e0;
+    __device__ uint32_t operator()(uint32_t o, bool live) const { return ld_u32(irs, 4u * (e0 + o), live); }
+};
+struct IdentityIndex {  // identity lists: computed, so the first digest loads issue at once
+    uint32_t e0;
+    __device__ uint32_t operator()(uint32_t o, bool) const { return e0 + o; }
+};
+
+// concat(digests[index(o)] for o < c): THE walk of a digest list, one lane per
+// list, for every kernel that hashes whole lists without waiting on their
+// digests.  Digests are prefetched one block ahead (cur: block b's), indices
+// two blocks ahead (nx0 / nx1: block b + 1's); a slot at or past c is dead
+// (zeros, no memory access).  kNulls: saw_null reports a live index equal to
+// kNullIndex (sha256_lists_kernel's optimistic pass; every other list is
+// compacted).
+template <class Index, bool kNulls = false>
+struct ListBlocks {
+    __amdgpu_buffer_rsrc_t drs;
+    Index index;
+    uint32_t c, L, nb;
     uint4 cur[4];
     uint32_t nx0, nx1;
-    __device__ void start(const uint8_t* digests, uint32_t n_digests, const uint32_t* cidx, uint32_t n_entries,
-                          uint32_t e0_, uint32_t c_, uint32_t nb_) {
-        drs = __builtin_amdgcn_make_buffer_rsrc((void*)digests, (short)0, (int)(32u * n_digests), 0x00020000);
-        irs = __builtin_amdgcn_make_buffer_rsrc((void*)cidx, (short)0, (int)(4u * n_entries), 0x00020000);
-        e0 = e0_;
+    bool saw_null;
+    __device__ void start(__amdgpu_buffer_rsrc_t drs_, Index index_, uint32_t c_, uint32_t nb_) {
+        drs = drs_;
+        index = index_;
         c = c_;
         L = 32u * c;
         nb = nb_;
-        nx0 = ld_u32(irs, 4u * (e0 + 2u), 2u < c);
-        nx1 = ld_u32(irs, 4u * (e0 + 3u), 3u < c);
-        const uint32_t i0 = ld_u32(irs, 4u * e0, 0u < c), i1 = ld_u32(irs, 4u * (e0 + 1u), 1u < c);
+        nx0 = index(2u, 2u < c);
+        nx1 = index(3u, 3u < c);
+        const uint32_t i0 = index(0u, 0u < c), i1 = index(1u, 1u < c);
+        saw_null = kNulls && ((0u < c && i0 == kNullIndex) || (1u < c && i1 == kNullIndex));
         load_digest(drs, i0, 0u < c, cur[0], cur[1]);
         load_digest(drs, i1, 1u < c, cur[2], cur[3]);
     }
+    // Block blk's words (blocks 0, 1, 2, ... in order), after issuing block
+    // blk + 1's digests and block blk + 2's indices.
     __device__ void block(uint32_t blk, uint32_t w[16]) {
+        const uint32_t d0 = 2u * blk;  // the block's first digest ordinal
+        if constexpr (kNulls) saw_null |= (d0 + 2u < c && nx0 == kNullIndex) || (d0 + 3u < c && nx1 == kNullIndex);
         uint4 nxt[4];
-        load_digest(drs, nx0, 2u * blk + 2u < c, nxt[0], nxt[1]);
-        load_digest(drs, nx1, 2u * blk + 3u < c, nxt[2], nxt[3]);
-        const uint32_t nn0 = ld_u32(irs, 4u * (e0 + 2u * blk + 4u), 2u * blk + 4u < c);
-        const uint32_t nn1 = ld_u32(irs, 4u * (e0 + 2u * blk + 5u), 2u * blk + 5u < c);
-#pragma unroll
-        for (int half = 0; half < 2; half++) {
-            const uint32_t di = 2u * blk + (uint32_t)half;  // digest ordinal in the message
-            const uint4 x0 = cur[2 * half], x1 = cur[2 * half + 1];
-            // past the end the loads returned zeros; only the 0x80 marker is added
-            w[8 * half + 0] = __builtin_bswap32(x0.x) | (di == c ? 0x80000000u : 0u);
-            w[8 * half + 1] = __builtin_bswap32(x0.y); w[8 * half + 2] = __builtin_bswap32(x0.z);
-            w[8 * half + 3] = __builtin_bswap32(x0.w); w[8 * half + 4] = __builtin_bswap32(x1.x);
-            w[8 * half + 5] = __builtin_bswap32(x1.y); w[8 * half + 6] = __builtin_bswap32(x1.z);
-            w[8 * half + 7] = __builtin_bswap32(x1.w);
-        }
-        if (blk + 1u == nb) {
-            w[14] = L >> 29;
-            w[15] = L << 3;
-        }
+        load_digest(drs, nx0, d0 + 2u < c, nxt[0], nxt[1]);
+        load_digest(drs, nx1, d0 + 3u < c, nxt[2], nxt[3]);
+        const uint32_t nn0 = index(d0 + 4u, d0 + 4u < c);
+        const uint32_t nn1 = index(d0 + 5u, d0 + 5u < c);
+        list_block_words(cur, d0, c, w);
+        if (blk + 1u == nb) list_block_length(w, L);
 #pragma unroll
         for (int i = 0; i < 4; i++) cur[i] = nxt[i];
         nx0 = nn0;
@@ -1253,8 +1242,8 @@ __global__ __launch_bounds__(kPairThreads) void sha256_chain_pair_kernel(
     const uint32_t e0 = valid ? cfirst[k] : 0u;
     const uint32_t c = valid ? cfirst[k + 1] - e0 : 0u;
     const uint32_t nb = valid ? blocks_for_len(32u * c) : 0u;
-    ListBlocks src;
-    if (producer) src.start(digests, n_digests, cidx, n_entries, e0, c, nb);
+    ListBlocks<LoadedIndex> src;
+    if (producer) src.start(buffer_rsrc(digests, 32u * n_digests), {buffer_rsrc(cidx, 4u * n_entries), e0}, c, nb);
     uint32_t st[8];
     pair_loop(src, ring, producer, lane, nb, st);
     if (!producer && valid) store_digest(out, k, st);
@@ -1262,96 +1251,35 @@ __global__ __launch_bounds__(kPairThreads) void sha256_chain_pair_kernel(
 
 // Dependent pass: message k = concat(digests[idx[e]] for e in [first[k], first[k+1]))
 // skipping idx == kNullIndex (a null request's empty digest, client_tracker.go:840-847).
-// One lane per list.  These waves run few per SIMD, so every global read on
-// the chain is an unconditional, range-checked buffer load (no branch + wait
-// per element): indices are prefetched two blocks ahead, digests one block
-// ahead.  If any list of the wave holds null entries, the whole wave first
-// compacts its lists into `scratch` (same positions as idx) and reads there.
-// aux bit 31 (volatile) keeps hipcc from merging adjacent dword loads into a
-// dwordx2/x4, whose range check would zero in-range entries that share an
-// access with out-of-range ones at the end of the array (lowers to sc0 sc1:
-// L1 bypass, L2-served).
-constexpr int kNoMerge = (int)(1u << 31);
-__device__ __forceinline__ uint32_t ld_u32(__amdgpu_buffer_rsrc_t rs, uint32_t off, bool live) {
-    return __builtin_amdgcn_raw_buffer_load_b32(rs, live ? off : 0xFFFFFFF0u, 0, kNoMerge);
-}
-
-// Digest `id` through a range-checked descriptor: a dead slot (or an index
-// past n_digests) reads zeros instead of faulting, without a branch.
-__device__ __forceinline__ void load_digest(__amdgpu_buffer_rsrc_t rsrc, uint32_t id, bool live, uint4& x0,
-                                            uint4& x1) {
-    const uint32_t o = live ? 32u * id : 0xFFFFFFE0u;
-    const auto a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0);
-    const auto b = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + 16u, 0, 0);
-    x0 = make_uint4(a[0], a[1], a[2], a[3]);
-    x1 = make_uint4(b[0], b[1], b[2], b[3]);
-}
+// One lane per list (ListBlocks).  If any list of the wave holds null entries,
+// the whole wave first compacts its lists into `scratch` (same positions as
+// idx) and reads there.
 
 // Hash this lane's list whose non-null entries are read through `brs` at
 // [e0, e0 + c).  Returns true if a null marker was met (only possible on the
 // optimistic pass, where brs is the caller's idx and c = e1 - e0).
 __device__ __forceinline__ bool hash_list(__amdgpu_buffer_rsrc_t drs, __amdgpu_buffer_rsrc_t brs, uint32_t e0,
                                           uint32_t c, bool valid, uint32_t st[8]) {
-    const uint32_t L = 32u * c;
-    const uint32_t nb = valid ? blocks_for_len(L) : 0u;
+    const uint32_t nb = valid ? blocks_for_len(32u * c) : 0u;
     const uint32_t wave_nb = wave_max(nb);
 #pragma unroll
     for (int i = 0; i < 8; i++) st[i] = kH0[i];
-    bool saw_null = false;
-
-    // Pipeline registers: digests of block b (cur), indices of block b+1 (nx).
-    uint4 cur[4];
-    uint32_t nx0 = ld_u32(brs, 4u * (e0 + 2u), 2u < c), nx1 = ld_u32(brs, 4u * (e0 + 3u), 3u < c);
-    {
-        const uint32_t i0 = ld_u32(brs, 4u * e0, 0u < c), i1 = ld_u32(brs, 4u * (e0 + 1u), 1u < c);
-        saw_null |= (0u < c && i0 == kNullIndex) || (1u < c && i1 == kNullIndex);
-        load_digest(drs, i0, 0u < c, cur[0], cur[1]);
-        load_digest(drs, i1, 1u < c, cur[2], cur[3]);
-    }
+    ListBlocks<LoadedIndex, true> src;
+    src.start(drs, {brs, e0}, c, nb);
     for (uint32_t blk = 0; blk < wave_nb; blk++) {
-        // Issue block b+1's digests and block b+2's indices before compressing b.
-        const bool l0 = 2u * blk + 2u < c, l1 = 2u * blk + 3u < c;
-        saw_null |= (l0 && nx0 == kNullIndex) || (l1 && nx1 == kNullIndex);
-        uint4 nxt[4];
-        load_digest(drs, nx0, l0, nxt[0], nxt[1]);
-        load_digest(drs, nx1, l1, nxt[2], nxt[3]);
-        const uint32_t nn0 = ld_u32(brs, 4u * (e0 + 2u * blk + 4u), 2u * blk + 4u < c);
-        const uint32_t nn1 = ld_u32(brs, 4u * (e0 + 2u * blk + 5u), 2u * blk + 5u < c);
-        if (blk < nb) {
-            uint32_t w[16];
-#pragma unroll
-            for (int half = 0; half < 2; half++) {
-                const uint32_t di = 2u * blk + (uint32_t)half;  // digest ordinal in the message
-                const uint4 x0 = cur[2 * half], x1 = cur[2 * half + 1];
-                // Past the end the loads returned zeros; only the 0x80 marker is added.
-                w[8 * half + 0] = __builtin_bswap32(x0.x) | (di == c ? 0x80000000u : 0u);
-                w[8 * half + 1] = __builtin_bswap32(x0.y); w[8 * half + 2] = __builtin_bswap32(x0.z);
-                w[8 * half + 3] = __builtin_bswap32(x0.w); w[8 * half + 4] = __builtin_bswap32(x1.x);
-                w[8 * half + 5] = __builtin_bswap32(x1.y); w[8 * half + 6] = __builtin_bswap32(x1.z);
-                w[8 * half + 7] = __builtin_bswap32(x1.w);
-            }
-            if (blk + 1u == nb) {
-                w[14] = L >> 29;
-                w[15] = L << 3;
-            }
-            compress_asm_lat(st, w);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) cur[i] = nxt[i];
-        nx0 = nn0;
-        nx1 = nn1;
+        uint32_t w[16];
+        src.block(blk, w);
+        if (blk < nb) compress_asm_lat(st, w);
     }
-    return saw_null;
+    return src.saw_null;
 }
 
 __global__ __launch_bounds__(kBlockThreads) void sha256_lists_kernel(
     const uint8_t* __restrict__ digests, uint32_t n_digests, const uint32_t* __restrict__ idx,
     uint32_t n_entries, const uint32_t* __restrict__ first, uint32_t n_lists, uint32_t* __restrict__ scratch,
     uint8_t* __restrict__ out) {
-    const __amdgpu_buffer_rsrc_t drs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)digests, (short)0, (int)(32u * n_digests), 0x00020000);
-    const __amdgpu_buffer_rsrc_t irs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)idx, (short)0, (int)(4u * n_entries), 0x00020000);
+    const __amdgpu_buffer_rsrc_t drs = buffer_rsrc(digests, 32u * n_digests);
+    const __amdgpu_buffer_rsrc_t irs = buffer_rsrc(idx, 4u * n_entries);
     const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
     const bool valid = k < n_lists;
     const uint32_t e0 = valid ? first[k] : 0u;
@@ -1371,22 +1299,16 @@ __global__ __launch_bounds__(kBlockThreads) void sha256_lists_kernel(
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const __amdgpu_buffer_rsrc_t srs =
-            __builtin_amdgcn_make_buffer_rsrc((void*)scratch, (short)0, (int)(4u * n_entries), 0x00020000);
+        const __amdgpu_buffer_rsrc_t srs = buffer_rsrc(scratch, 4u * n_entries);
         (void)hash_list(drs, srs, e0, m, valid, st);
     }
     if (valid) store_digest(out, k, st);
 }
 
-// Pipelined dependent pass: one SEGMENT of every list's chain.  Lists are
-// compacted (no null entries).  Segment [ob, oe) hashes the full 2-digest
-// blocks of digest ordinals ob .. min(oe, c) (ob, oe even) starting from the
-// midstate in `state` (H0 when ob == 0); a list whose last digest falls in
-// the segment (c <= oe) is finalised (partial block + FIPS padding) and its
-// digest written to out, otherwise the midstate is written back.  Lists with
-// c <= ob (ob > 0) were finalised by an earlier segment and are skipped.
-// The waves raise their issue priority: they run beside the next request
-// chunk and must keep near-alone speed on their SIMD.
+// The plans' dependent pass: every list's whole chain from H0, one lane per
+// list (ListBlocks).  Lists are compacted (no null entries).  The waves raise
+// their issue priority: they run beside the next request chunk and must keep
+// near-alone speed on their SIMD.
 // kUni (uni = B > 0): identity lists of B entries -- list k is digests
 // [k B, min(k B + B, n_entries)), the BatchSize batches over consecutive
 // requests of a plan (mirsha_plan.hip detects them) -- so bounds and indices
@@ -1399,13 +1321,9 @@ __global__ __launch_bounds__(kBlockThreads) void sha256_lists_kernel(
 template <bool kUni>
 __global__ __launch_bounds__(kBlockThreads) void sha256_chain_kernel(
     const uint8_t* __restrict__ digests, uint32_t n_digests, const uint32_t* __restrict__ cidx,
-    uint32_t n_entries, const uint32_t* __restrict__ cfirst, uint32_t n_lists, uint32_t ob, uint32_t oe,
-    uint32_t* __restrict__ state, uint8_t* __restrict__ out, uint32_t uni, PadBlockKW pad) {
+    uint32_t n_entries, const uint32_t* __restrict__ cfirst, uint32_t n_lists, uint8_t* __restrict__ out,
+    uint32_t uni, PadBlockKW pad) {
     __builtin_amdgcn_s_setprio(3);
-    const __amdgpu_buffer_rsrc_t drs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)digests, (short)0, (int)(32u * n_digests), 0x00020000);
-    const __amdgpu_buffer_rsrc_t irs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)cidx, (short)0, (int)(4u * n_entries), 0x00020000);
     const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
     const bool valid = k < n_lists;
     uint32_t e0, c;
@@ -1416,89 +1334,40 @@ __global__ __launch_bounds__(kBlockThreads) void sha256_chain_kernel(
         e0 = valid ? cfirst[k] : 0u;
         c = valid ? cfirst[k + 1] - e0 : 0u;
     }
-    // digest index of ordinal o of this list (0 for a dead slot: never read live)
-    auto index = [&](uint32_t o, bool lv) -> uint32_t {
-        if constexpr (kUni)
-            return e0 + o;
-        else
-            return ld_u32(irs, 4u * (e0 + o), lv);
-    };
-    const bool active = valid && (ob == 0u || c > ob);
-    const bool fin = active && c <= oe;
-    const uint32_t full_end = fin ? (c & ~1u) : oe;  // exclusive ordinal of the full blocks
-    const uint32_t nblk = active ? (full_end - ob) / 2u + (fin ? 1u : 0u) : 0u;
-    const uint32_t wave_nb = wave_max(nblk);
-    const uint32_t L = 32u * c;
+    const uint32_t nb = valid ? blocks_for_len(32u * c) : 0u;
+    const uint32_t wave_nb = wave_max(nb);
     // wave-uniform: every lane finishes a full list of B (even) entries here
-    const bool pad_wave = kUni && pad.use && __all(fin && c == uni);
+    const bool pad_wave = kUni && pad.use && __all(valid && c == uni);
 
     uint32_t st[8];
-    if (ob == 0u || !active) {
 #pragma unroll
-        for (int i = 0; i < 8; i++) st[i] = kH0[i];
-    } else {
-        const uint4* sp = reinterpret_cast<const uint4*>(state + 8ull * k);
-        const uint4 s0 = sp[0], s1 = sp[1];
-        st[0] = s0.x; st[1] = s0.y; st[2] = s0.z; st[3] = s0.w;
-        st[4] = s1.x; st[5] = s1.y; st[6] = s1.z; st[7] = s1.w;
+    for (int i = 0; i < 8; i++) st[i] = kH0[i];
+    ListBlocks<std::conditional_t<kUni, IdentityIndex, LoadedIndex>> src;
+    if constexpr (kUni)
+        src.start(buffer_rsrc(digests, 32u * n_digests), {e0}, c, nb);
+    else
+        src.start(buffer_rsrc(digests, 32u * n_digests), {buffer_rsrc(cidx, 4u * n_entries), e0}, c, nb);
+    // A pad_wave's last block holds no digest and runs after the loop, so the
+    // 64 SGPRs of pad.kw are not live across it (inside the loop they cost the
+    // eighth wave per SIMD).
+    const uint32_t data_nb = pad_wave ? wave_nb - 1u : wave_nb;
+    for (uint32_t blk = 0; blk < data_nb; blk++) {
+        uint32_t w[16];
+        src.block(blk, w);
+        if (blk < nb) compress_asm_lat(st, w);
     }
-
-    // Same prefetch pipeline as hash_list: digests one block ahead, indices two.
-    auto live = [&](uint32_t t, uint32_t slot) { return t < nblk && ob + 2u * t + slot < c; };
-    uint4 cur[4];
-    uint32_t nx0 = index(ob + 2u, live(1, 0)), nx1 = index(ob + 3u, live(1, 1));
-    {
-        const uint32_t i0 = index(ob, live(0, 0));
-        const uint32_t i1 = index(ob + 1u, live(0, 1));
-        load_digest(drs, i0, live(0, 0), cur[0], cur[1]);
-        load_digest(drs, i1, live(0, 1), cur[2], cur[3]);
+    if (pad_wave) {  // the padding-only final block
+        uint32_t s[8];
+#pragma unroll
+        for (int i = 0; i < 8; i++) s[i] = st[i];
+#pragma unroll
+        for (int g = 0; g < 8; g++)
+            rounds_kw8_asm(s, make_uint4(pad.kw[8 * g], pad.kw[8 * g + 1], pad.kw[8 * g + 2], pad.kw[8 * g + 3]),
+                           make_uint4(pad.kw[8 * g + 4], pad.kw[8 * g + 5], pad.kw[8 * g + 6], pad.kw[8 * g + 7]));
+#pragma unroll
+        for (int i = 0; i < 8; i++) st[i] += s[i];
     }
-    for (uint32_t t = 0; t < wave_nb; t++) {
-        uint4 nxt[4];
-        load_digest(drs, nx0, live(t + 1, 0), nxt[0], nxt[1]);
-        load_digest(drs, nx1, live(t + 1, 1), nxt[2], nxt[3]);
-        const uint32_t nn0 = index(ob + 2u * t + 4u, live(t + 2, 0));
-        const uint32_t nn1 = index(ob + 2u * t + 5u, live(t + 2, 1));
-        if (pad_wave && t + 1u == wave_nb) {  // the padding-only final block
-            uint32_t s[8];
-#pragma unroll
-            for (int i = 0; i < 8; i++) s[i] = st[i];
-#pragma unroll
-            for (int g = 0; g < 8; g++)
-                rounds_kw8_asm(s, make_uint4(pad.kw[8 * g], pad.kw[8 * g + 1], pad.kw[8 * g + 2], pad.kw[8 * g + 3]),
-                               make_uint4(pad.kw[8 * g + 4], pad.kw[8 * g + 5], pad.kw[8 * g + 6], pad.kw[8 * g + 7]));
-#pragma unroll
-            for (int i = 0; i < 8; i++) st[i] += s[i];
-        } else if (t < nblk) {
-            uint32_t w[16];
-#pragma unroll
-            for (int half = 0; half < 2; half++) {
-                const uint32_t di = ob + 2u * t + (uint32_t)half;
-                const uint4 x0 = cur[2 * half], x1 = cur[2 * half + 1];
-                w[8 * half + 0] = __builtin_bswap32(x0.x) | (fin && di == c ? 0x80000000u : 0u);
-                w[8 * half + 1] = __builtin_bswap32(x0.y); w[8 * half + 2] = __builtin_bswap32(x0.z);
-                w[8 * half + 3] = __builtin_bswap32(x0.w); w[8 * half + 4] = __builtin_bswap32(x1.x);
-                w[8 * half + 5] = __builtin_bswap32(x1.y); w[8 * half + 6] = __builtin_bswap32(x1.z);
-                w[8 * half + 7] = __builtin_bswap32(x1.w);
-            }
-            if (fin && t + 1u == nblk) {
-                w[14] = L >> 29;
-                w[15] = L << 3;
-            }
-            compress_asm_lat(st, w);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) cur[i] = nxt[i];
-        nx0 = nn0;
-        nx1 = nn1;
-    }
-    if (fin) {
-        store_digest(out, k, st);
-    } else if (active) {
-        uint4* sp = reinterpret_cast<uint4*>(state + 8ull * k);
-        sp[0] = make_uint4(st[0], st[1], st[2], st[3]);
-        sp[1] = make_uint4(st[4], st[5], st[6], st[7]);
-    }
+    if (valid) store_digest(out, k, st);
 }
 
 // ---- fused request -> list pass: ONE launch ---------------------------------
@@ -1597,7 +1466,8 @@ __device__ __forceinline__ void load_digest_sc1(__amdgpu_buffer_rsrc_t rsrc, uin
 // a time, double-buffered in registers, so one chunk's digest loads (sc1,
 // served from MALL/HBM under full request load: several us) are in flight
 // while the previous chunk is compressed.  Indices are static and loaded a
-// chunk ahead.  (2-block chunks: the launch's 1024-thread tile blocks hold the
+// chunk ahead.  (Not ListBlocks: a chunk's digests may only be requested once
+// its readiness counter has been reached.)  (2-block chunks: the launch's 1024-thread tile blocks hold the
 // kernel to 128 VGPRs.)
 constexpr uint32_t kChunkDigests = 2u * kFusedChunkBlocks;
 __device__ __forceinline__ void load_chunk_idx(__amdgpu_buffer_rsrc_t irs, uint32_t e0, uint32_t c, uint32_t chunk,
@@ -1732,20 +1602,8 @@ __device__ __forceinline__ bool fused_list_produce(const FusedArgs& a, __amdgpu_
             const uint32_t blk = kFusedChunkBlocks * chunk + j;
             if (blk < wave_nb) {  // wave-uniform: dead lanes hand over words the consumer ignores
                 uint32_t w[16];
-#pragma unroll
-                for (int half = 0; half < 2; half++) {
-                    const uint32_t di = 2u * blk + (uint32_t)half;
-                    const uint4 x0 = dc[4 * j + 2 * half], x1 = dc[4 * j + 2 * half + 1];
-                    w[8 * half + 0] = __builtin_bswap32(x0.x) | (di == c ? 0x80000000u : 0u);
-                    w[8 * half + 1] = __builtin_bswap32(x0.y); w[8 * half + 2] = __builtin_bswap32(x0.z);
-                    w[8 * half + 3] = __builtin_bswap32(x0.w); w[8 * half + 4] = __builtin_bswap32(x1.x);
-                    w[8 * half + 5] = __builtin_bswap32(x1.y); w[8 * half + 6] = __builtin_bswap32(x1.z);
-                    w[8 * half + 7] = __builtin_bswap32(x1.w);
-                }
-                if (blk + 1u == sh.nb) {
-                    w[14] = L >> 29;
-                    w[15] = L << 3;
-                }
+                list_block_words(&dc[4 * j], 2u * blk, c, w);
+                if (blk + 1u == sh.nb) list_block_length(w, L);
                 // slot seq & 1 was last filled with block seq - 2: free once seq - 1 blocks are consumed
                 if (seq >= 2u && !lds_wait_ge(&ring.consumed, seq - 1u, a.err)) return fused_abort(ring);
                 produce_kw(w, ring.kw[seq & 1u], lane);
@@ -2143,25 +2001,10 @@ __global__ void gen_mixed_kernel(uint64_t seed, uint64_t first, uint64_t count, 
 }
 
 // ---- launching ------------------------------------------------------------
+// (launch_k: mirsha_device.h)
 LaunchEvents& next_launch_events() {
     thread_local LaunchEvents ev;
     return ev;
-}
-
-// Every kernel of the library is launched here: with the thread's pending
-// timing events bound to the dispatch (hipExtLaunchKernel) when a timed
-// launch set them, else a plain launch.  Errors are left for the caller's
-// hipGetLastError, as with <<<...>>>.
-template <typename... P, typename... A>
-void launch_k(void (*k)(P...), dim3 grid, dim3 block, uint32_t shmem, hipStream_t s, A... args) {
-    LaunchEvents& ev = next_launch_events();
-    if (ev.start && ev.stop) {
-        const hipEvent_t e0 = ev.start, e1 = ev.stop;
-        ev = LaunchEvents{};
-        hipExtLaunchKernelGGL(k, grid, block, shmem, s, e0, e1, 0u, static_cast<P>(args)...);
-    } else {
-        k<<<grid, block, shmem, s>>>(static_cast<P>(args)...);
-    }
 }
 
 // ---- clock probe (bench diagnostics; no digest depends on it) ---------------
@@ -2347,8 +2190,7 @@ PadBlockKW pad_block_kw(uint64_t L) {
 }
 
 hipError_t launch_chain(const uint8_t* digests, uint32_t n_digests, const uint32_t* cidx, uint32_t n_entries,
-                        const uint32_t* cfirst, uint32_t n_lists, uint32_t ob, uint32_t oe, uint32_t* state,
-                        uint8_t* out, hipStream_t s, uint32_t uniform) {
+                        const uint32_t* cfirst, uint32_t n_lists, uint8_t* out, hipStream_t s, uint32_t uniform) {
     if (n_lists == 0) return hipSuccess;
     const uint32_t grid = (n_lists + kBlockThreads - 1u) / kBlockThreads;
     if (uniform) {
@@ -2362,10 +2204,10 @@ hipError_t launch_chain(const uint8_t* digests, uint32_t n_digests, const uint32
             pad.use = !(e && e[0] == '0');
         }
         launch_k(sha256_chain_kernel<true>, grid, kBlockThreads, 0, s, digests, n_digests, cidx, n_entries, cfirst,
-                 n_lists, ob, oe, state, out, uniform, pad);
+                 n_lists, out, uniform, pad);
     } else {
         launch_k(sha256_chain_kernel<false>, grid, kBlockThreads, 0, s, digests, n_digests, cidx, n_entries, cfirst,
-                 n_lists, ob, oe, state, out, 0u, PadBlockKW{});
+                 n_lists, out, 0u, PadBlockKW{});
     }
     return hipGetLastError();
 }
@@ -2412,10 +2254,8 @@ __device__ __forceinline__ void load_digest_words(const uint8_t* __restrict__ di
     if (live) {
         const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * p);
         const uint4 a = d[0], b = d[1];
-        w[0] = __builtin_bswap32(a.x); w[1] = __builtin_bswap32(a.y);
-        w[2] = __builtin_bswap32(a.z); w[3] = __builtin_bswap32(a.w);
-        w[4] = __builtin_bswap32(b.x); w[5] = __builtin_bswap32(b.y);
-        w[6] = __builtin_bswap32(b.z); w[7] = __builtin_bswap32(b.w);
+        be_words(a, w);
+        be_words(b, w + 4);
     } else {
 #pragma unroll
         for (int i = 0; i < 8; i++) w[i] = 0u;
@@ -2533,66 +2373,10 @@ __global__ __launch_bounds__(kBlockThreads) void chains_reset_kernel(const uint3
 //
 // Which entries a step consumes depends on the entry kinds and the parity
 // only, never on a hash value, so the lane's walk over its programme
-// (commit_fetch) runs one step ahead of the hashing: the next step's entries
+// (commit_fetch, mirsha_device.h) runs one step ahead of the hashing: the next step's entries
 // were loaded a step earlier, its digest rows are requested before this
 // step's compression and first touched (byte swap) after it.  A lone lane
 // then pays max(compression, one load) per step, not their sum.
-struct CommitStep {
-    uint4 a0, a1, b0, b1;  // raw rows of the two halves (zeros where the step loads none)
-    uint64_t bits;         // checkpoint: the message's bit length
-    uint32_t row;          // checkpoint: output row
-    bool use_pend;         // first half = the pending digest
-    bool have_a;           // checkpoint: a first half precedes the 0x80
-    bool write, cp;        // compress two digests / the final block (neither: nothing to hash)
-    bool keep;             // a lone last write: the first half becomes the pending digest
-};
-
-// Plans step t of a lane at entry e (x0 = ent[e], xn = ent[e + 1], each
-// loaded only below `end`), requests its digest rows, moves e and the digest
-// count n past it and loads the entries of step t + 1.  Every load is guarded
-// by the lane's own range: past `end` the index would run into the next
-// chain's entries or beyond the array (the note on pos in
-// chains_absorb_kernel).
-__device__ __forceinline__ CommitStep commit_fetch(const uint8_t* __restrict__ digests,
-                                                   const uint32_t* __restrict__ ent, uint32_t end, uint32_t& e,
-                                                   uint64_t& n, uint32_t& x0, uint32_t& xn) {
-    CommitStep s;
-    const bool live = e < end;
-    const bool odd = (n & 1u) != 0u;
-    const bool take0 = live && !odd && !(x0 & kCommitEntryCheckpoint);  // first half from the table
-    const uint32_t e1 = e + (take0 ? 1u : 0u);
-    const bool live1 = live && e1 < end;  // odd && live: e1 == e, so live1
-    const uint32_t x1 = take0 ? xn : x0;
-    s.write = live1 && !(x1 & kCommitEntryCheckpoint);
-    s.cp = live1 && (x1 & kCommitEntryCheckpoint) != 0u;
-    s.use_pend = odd && live1;
-    s.have_a = odd || take0;
-    s.keep = take0 && !live1;
-    s.row = x1 & ~kCommitEntryCheckpoint;
-    s.bits = (n + (take0 ? 1u : 0u)) * 256u;
-    s.a0 = s.a1 = s.b0 = s.b1 = make_uint4(0u, 0u, 0u, 0u);
-    if (take0) {
-        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x0);
-        s.a0 = d[0];
-        s.a1 = d[1];
-    }
-    if (s.write) {
-        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x1);
-        s.b0 = d[0];
-        s.b1 = d[1];
-    }
-    n = s.cp ? 0u : n + (take0 ? 1u : 0u) + (s.write ? 1u : 0u);
-    e = e1 + (live1 ? 1u : 0u);
-    x0 = e < end ? ent[e] : 0u;
-    xn = e + 1u < end ? ent[e + 1u] : 0u;  // e <= end <= 2^31: no wrap
-    return s;
-}
-
-__device__ __forceinline__ void be_words(const uint4& v, uint32_t w[4]) {
-    w[0] = __builtin_bswap32(v.x); w[1] = __builtin_bswap32(v.y);
-    w[2] = __builtin_bswap32(v.z); w[3] = __builtin_bswap32(v.w);
-}
-
 __global__ __launch_bounds__(kBlockThreads) void chains_commit_kernel(
     const uint8_t* __restrict__ digests, const uint32_t* __restrict__ ent, const uint32_t* __restrict__ act,
     const uint32_t* __restrict__ efirst, uint32_t n_active, uint32_t* __restrict__ h, uint32_t* __restrict__ pend,

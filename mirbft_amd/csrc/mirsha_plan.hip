@@ -64,7 +64,6 @@ int pipeline_build(mirsha_ctx* c, mirsha_pipeline* p, uint32_t n_req, const uint
     HIP_TRY(c, p->d_cidx.ensure(sizeof(uint32_t) * std::max<uint32_t>(p->n_entries, 1)));
     HIP_TRY(c, p->d_cfirst.ensure(sizeof(uint32_t) * (n_lists + 1)));
     HIP_TRY(c, p->d_order.ensure(sizeof(uint32_t) * std::max<uint32_t>(n_req, 1)));
-    HIP_TRY(c, p->d_state.ensure(32ull * std::max<uint32_t>(n_lists, 1)));
     // Copies on the context stream (not the legacy null stream); the host
     // vectors must outlive them, hence the synchronize.
     if (p->n_entries)
@@ -94,8 +93,7 @@ int pipeline_run(mirsha_ctx* c, mirsha_pipeline* p, const uint8_t* d_arena, uint
         });
     return timed_launch(c, 1, [&] {
         return mirsha::launch_chain(d_req_out, p->n_req, p->d_cidx.as<uint32_t>(), p->n_entries,
-                                    p->d_cfirst.as<uint32_t>(), p->n_lists, 0u, mirsha::kOpenEnd,
-                                    p->d_state.as<uint32_t>(), d_list_out, c->stream, p->uniform);
+                                    p->d_cfirst.as<uint32_t>(), p->n_lists, d_list_out, c->stream, p->uniform);
     });
 }
 
@@ -479,7 +477,6 @@ void pipeline_free(mirsha_pipeline* p) {
     p->d_cidx.release();
     p->d_cfirst.release();
     p->d_order.release();
-    p->d_state.release();
     p->d_tadj_first.release();
     p->d_tadj.release();
     p->d_cbase.release();

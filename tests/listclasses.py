@@ -8,7 +8,8 @@ Every form of the dependent pass gives one lane a list and decides per 64 lists:
                 a null entry, compacts all 64 lists into scratch and hashes again
   wave_nb       wave_max of the lists' block counts (a list of c digests has
                 (32 c + 72) >> 6 blocks): every lane loops that far and pads by
-                `di == c` on zero-filled, range-checked loads
+                `ordinal == c` on zero-filled, range-checked loads
+                (list_block_words)
   pad_wave      sha256_chain_kernel<true>: __all lists full with an even count,
                 then the final block runs from a constant schedule
   chunks        the fused producer waits per ceil(wave_nb / kFusedChunkBlocks)
@@ -38,8 +39,8 @@ INDICES = ("distinct", "edge", "shared")
 ONE_LONG = 41
 # each_one: one null per lane at a seeded position, at 2 or later where the list
 # has more than two entries; the first lanes long enough get theirs at these
-# positions, the entries hash_list / ListBlocks hold prefetched in nx0 / nx1 and
-# nn0 / nn1.
+# positions, the entries ListBlocks (the list source of the lists, pair and
+# chain kernels) holds prefetched in nx0 / nx1 and nn0 / nn1.
 PREFETCHED = (2, 3, 4, 5)
 
 RAW_NULLS = ("none", "one_lane", "several_lanes")

@@ -3,13 +3,17 @@
 The dependent pass (batch, VerifyBatch and checkpoint-list digests over
 request digests) has six forms in mirbft_amd/csrc/mirsha_kernels.hip:
 sha256_lists_kernel (optimistic hash_list, a wave-wide null ballot, compaction
-into scratch and a second pass), sha256_chain_pair_kernel (ListBlocks +
-pair_loop), sha256_chain_kernel<false> (loaded bounds and indices) and <true>
-(computed ones, with the constant-schedule block of a pad_wave), overlap_chain,
-and fused_list_produce / fused_list_consume.  Each gives one lane a list,
-decides with predicates over 64 lists (null ballot, wave_max of the block
-counts, pad_wave), pads by `di == c` on zero-filled range-checked loads, and
-reads indices through a descriptor that ends exactly at n_entries.
+into scratch and a second pass), sha256_chain_pair_kernel (pair_loop),
+sha256_chain_kernel<false> (loaded bounds and indices) and <true> (computed
+ones, with the constant-schedule block of a pad_wave), overlap_chain, and
+fused_list_produce / fused_list_consume.  The first four walk their lists
+through the one prefetching source, ListBlocks (loaded or computed indices,
+the null report switched on for the lists kernel alone); the last two keep
+load schedules of their own.  All six build a block with list_block_words
+(mirsha_device.h).  Each gives one lane a list, decides with predicates over
+64 lists (null ballot, wave_max of the block counts, pad_wave), pads by
+`ordinal == c` on zero-filled range-checked loads, and reads indices through
+a descriptor that ends exactly at n_entries.
 
 tests/listclasses.py builds one stream of 273 whole groups (17,472 lists) over
 1,024 digests, the product of
@@ -54,12 +58,9 @@ __all fails test_identity_lists for every even B at 513 x 64 and 513 x 64 + 63
 lists, a short last list beside full ones; an overlap_chain that takes wave_nb
 from lane 0 fails all of test_sequential_plans_routed; a loaded-index chain
 kernel that does the same fails only its 513-group case.  The older
-BatchSize and irregular streams catch these three as well.
-
-Not covered: the `ob > 0` segment path of sha256_chain_kernel (midstates
-through `state`).  It is unreachable from the product: launch_chain is only
-ever called with (0, kOpenEnd) and mirsha_pipeline_segments always reports
-one segment.
+BatchSize and irregular streams catch these three as well.  (The mutants were
+of the kernels as they stood before ListBlocks became the one list source; the
+predicates they broke are the same.)
 """
 import hashlib
 
