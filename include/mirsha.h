@@ -101,7 +101,11 @@ int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
  * and clock probe, 3 = batch-chain kernel, 4 = fused request -> batch kernel
  * (one persistent launch per run), 5 = overlapped-cycles kernel
  * (mirsha_pipeline_overlap_device), 6 = digest compare kernel (mirsha_verify_*),
- * 7 = select kernel of the mixed ring submissions (mirsha_submit_*_expect).
+ * 7 = select kernel of the mixed ring submissions (mirsha_submit_*_expect),
+ * 8 = the kernels of the device-built bucket order (mirsha_bucket_order_device,
+ * MIRSHA_ORDER_DEVICE): the count and the scatter kernel, two launches per
+ * built order (rocPRIM's scan between them is not timed), or the one identity
+ * launch.
  * set_timing_mask: bit k on = kernel k is timed while timing is enabled
  * (default: all). */
 int mirsha_ctx_set_timing(mirsha_ctx* ctx, int enable);
@@ -517,6 +521,70 @@ int mirsha_pipeline_overlap_device(mirsha_ctx* ctx, mirsha_pipeline* p, const ui
  * longest first (stable), so a wave's 64 lanes run equal-length chains.
  * Returns 1 if the order is the identity (all lengths in one bucket), else 0. */
 int mirsha_bucket_order(const uint32_t* len, uint32_t n, uint32_t* order_out);
+
+/* The same order built on the device, from lengths that are already there: a
+ * counting sort in three launches in stream order (per-wave histograms of
+ * `chunk` messages each, one exclusive scan of the bin-major counts, a stable
+ * scatter).  The caller knows bounds on the lengths: with blocks(L) =
+ * ceil((L + 9) / 64) there are bins = blocks(max_len) - blocks(min_len) + 1
+ * bins and message i's bin is clamp(blocks(max_len) - blocks(len[i]), 0,
+ * bins - 1).  A length outside [min_len, max_len] therefore sorts as the
+ * nearest bound and the result is a permutation of 0..n-1 whatever the
+ * lengths are; when every length lies inside the bounds it equals
+ * mirsha_bucket_order's output element for element.
+ * At most MIRSHA_ORDER_MAX_BINS bins (a wave's histogram lives in its LDS:
+ * 16 KiB, block counts spread over 256 KiB of message length). */
+#define MIRSHA_ORDER_MAX_BINS 4096
+
+/* Host-only (no context): the shape of those launches for n messages with
+ * lengths in [min_len, max_len].  *bins_out as above; MIRSHA_ERANGE when it
+ * exceeds MIRSHA_ORDER_MAX_BINS (the other outputs are then 0).  chunk =
+ * max(1024, bins rounded up to a multiple of 64) message indices per wave,
+ * n_chunks = ceil(n / chunk) waves, scratch_bytes = 8 * bins * n_chunks (the
+ * counts and their scan, u32 each) <= 8 n + 65536 because chunk >= bins; the
+ * scan's own temporary storage (rocPRIM's, a few KiB) is not included.
+ * MIRSHA_EINVAL: min_len > max_len or a NULL output. */
+int mirsha_order_plan(uint32_t n, uint32_t min_len, uint32_t max_len, uint32_t* bins_out, uint32_t* chunk_out,
+                      uint32_t* n_chunks_out, uint64_t* scratch_bytes_out);
+
+/* Queues that sort on the context's stream, with no synchronisation (device
+ * pointers, as the other _device forms): d_order_out[0, n) = the bucket order
+ * of d_len[0, n).  The scratch is a grow-only buffer of the context, safe
+ * because every call's launches run on one stream.
+ * Returns 0, or 1 when bins == 1: one launch then writes the identity, and
+ * the caller may pass NULL as d_order downstream.  n == 0 is valid, queues
+ * nothing and returns 1.  MIRSHA_ERANGE: more than MIRSHA_ORDER_MAX_BINS bins,
+ * nothing is queued and d_order_out is untouched.  MIRSHA_EINVAL: min_len >
+ * max_len, or a NULL pointer with n > 0. */
+int mirsha_bucket_order_device(mirsha_ctx* ctx, const uint32_t* d_len, uint32_t n, uint32_t min_len,
+                               uint32_t max_len, uint32_t* d_order_out);
+
+/* d_off_out[i] = d_len[0] + ... + d_len[i-1] (u64; the exclusive scan the
+ * gapless host routes run), device pointers, queued on the context's stream
+ * with no synchronisation.  With it the chain lengths -> offsets -> order ->
+ * mirsha_hash_batch_device needs no host array.  n == 0 queues nothing;
+ * MIRSHA_EINVAL: a NULL pointer with n > 0. */
+int mirsha_offsets_device(mirsha_ctx* ctx, const uint32_t* d_len, uint32_t n, uint64_t* d_off_out);
+
+/* Where mirsha_submit_batch / mirsha_submit_batch_expect build the bucket
+ * order of a cycle whose block counts differ.
+ *   MIRSHA_ORDER_HOST (default): mirsha_bucket_order on the submitting thread,
+ *     the order's 4 n bytes cross PCIe with the metadata.
+ *   MIRSHA_ORDER_DEVICE: the three launches above on the context's stream,
+ *     behind the arrival of the lengths and ahead of the hashing kernel, with
+ *     the validation pass's exact bounds: the same order, the same digests,
+ *     no sort in the caller's time and 4 n bytes less over PCIe.  A cycle of
+ *     one block count has the identity order and no order launch in either
+ *     mode; one whose block counts spread over more than MIRSHA_ORDER_MAX_BINS
+ *     takes the host route.
+ * Every other entry point (slice submissions, the synchronous calls, the
+ * mirsha_multi_* forms' own contexts unless set through mirsha_multi_ctx)
+ * sorts on the host in both modes.  Anything else is MIRSHA_EINVAL.
+ * mirsha_ctx_order_mode returns the mode (MIRSHA_EINVAL for a NULL context). */
+#define MIRSHA_ORDER_HOST 0
+#define MIRSHA_ORDER_DEVICE 1
+int mirsha_ctx_set_order_mode(mirsha_ctx* ctx, int mode);
+int mirsha_ctx_order_mode(const mirsha_ctx* ctx);
 
 /* ------------------------------------- streaming checkpoint chains (f4) */
 /* Device-resident running SHA-256 states, one per application node: the

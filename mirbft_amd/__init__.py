@@ -9,7 +9,7 @@ from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
 from .engine import (CheckpointChains, CommitTicket, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order,
                      commit_plan, commit_seg_plan, dedup_plan, dedup_rows, device_count, expect_bitmap, expect_plan, hash_batch_multi,
-                     mismatch_indices)
+                     mismatch_indices, order_plan)
 from .processor import (ActionResults, Actions, Checkpoint, CheckpointResult, Commit, CommitBatch, DeviceLog, GpuHash,
                         HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, commit_programme,
                         gpu_hasher)
@@ -37,6 +37,7 @@ __all__ = [
     "MirshaError",
     "MirshaUnavailable",
     "bucket_order",
+    "order_plan",
     "device_count",
     "hash_batch_multi",
     "MultiEngine",

@@ -28,6 +28,9 @@ MIRSHA_COMMIT_SEG_LAST = 2
 MIRSHA_MAX_MESSAGE_BYTES = 0xFFFFFF00
 MIRSHA_MAX_DEVICE_ARENA_BYTES = 0xFFFFFF00
 MIRSHA_SUBMIT_DEDUP = 1
+MIRSHA_ORDER_MAX_BINS = 4096
+MIRSHA_ORDER_HOST = 0
+MIRSHA_ORDER_DEVICE = 1
 
 ERROR_NAMES = {
     MIRSHA_EINVAL: "EINVAL",
@@ -118,6 +121,11 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p],
     ),
     "mirsha_bucket_order": (c_int, [c_void_p, c_uint32, c_void_p]),
+    "mirsha_order_plan": (c_int, [c_uint32, c_uint32, c_uint32, _u32p, _u32p, _u32p, _u64p]),
+    "mirsha_bucket_order_device": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p]),
+    "mirsha_offsets_device": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+    "mirsha_ctx_set_order_mode": (c_int, [c_void_p, c_int]),
+    "mirsha_ctx_order_mode": (c_int, [c_void_p]),
     "mirsha_pipeline_create": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mirsha_pipeline_create_mode": (
         c_int,

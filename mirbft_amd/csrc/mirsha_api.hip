@@ -1,7 +1,7 @@
 // mirsha_api.hip — host side of the C-ABI declared in include/mirsha.h:
 // contexts, timing, the device-pointer API (the digest compare of
-// mirsha_verify_* among it), synthetic streams, streaming
-// checkpoint chains and the clock probe.  The other host units are listed in
+// mirsha_verify_* among it, and the bucket order and the offsets built on the
+// device), synthetic streams, streaming checkpoint chains and the clock probe.  The other host units are listed in
 // mirsha_ctx.h.
 #include "mirsha_ctx.h"
 
@@ -98,6 +98,36 @@ int queue_verify(mirsha_ctx* c, const uint8_t* d_digests, const uint8_t* d_expec
     });
 }
 
+int order_buffers(mirsha_ctx* c, uint32_t n, uint32_t bmin, uint32_t bmax, OrderShape* shape) {
+    OrderShape& sh = *shape;
+    sh.bmax = bmax;
+    sh.bins = bmax - bmin + 1u;
+    sh.chunk = mirsha::host::order_chunk(sh.bins);
+    sh.n_chunks = (uint32_t)(((uint64_t)n + sh.chunk - 1u) / sh.chunk);
+    const size_t cells = (size_t)sh.bins * sh.n_chunks;
+    sh.scan_bytes = 0;
+    HIP_TRY(c, mirsha::launch_counts_scan(nullptr, sh.scan_bytes, nullptr, nullptr, cells, c->stream));
+    HIP_TRY(c, c->d_scan.ensure(std::max<size_t>(sh.scan_bytes, 4)));
+    HIP_TRY(c, c->d_order_counts.ensure(std::max<size_t>(8u * cells, 8)));
+    return MIRSHA_OK;
+}
+
+int queue_bucket_order(mirsha_ctx* c, const OrderShape& sh, const uint32_t* d_len, uint32_t n, uint32_t* d_order) {
+    uint32_t* counts = c->d_order_counts.as<uint32_t>();
+    const size_t cells = (size_t)sh.bins * sh.n_chunks;
+    uint32_t* base = counts + cells;
+    if (int rc = timed_launch(c, kTimerOrder, [&] {
+            return mirsha::launch_order_count(d_len, n, sh.bmax, sh.bins, sh.chunk, sh.n_chunks, counts, c->stream);
+        }))
+        return rc;
+    size_t scan_bytes = sh.scan_bytes;
+    HIP_TRY(c, mirsha::launch_counts_scan(c->d_scan.p, scan_bytes, counts, base, cells, c->stream));
+    return timed_launch(c, kTimerOrder, [&] {
+        return mirsha::launch_order_scatter(d_len, n, sh.bmax, sh.bins, sh.chunk, sh.n_chunks, base, d_order,
+                                            c->stream);
+    });
+}
+
 }  // namespace mirsha_api
 
 extern "C" {
@@ -152,6 +182,7 @@ void mirsha_ctx_destroy(mirsha_ctx* c) {
     c->d_arena.release(); c->d_off.release(); c->d_len.release(); c->d_order.release();
     c->d_out.release(); c->d_idx.release(); c->d_first.release(); c->d_out2.release(); c->d_scratch.release();
     c->d_scan.release();
+    c->d_order_counts.release();
     for (int k = 0; k < kStageSlots; k++) {
         c->h_ring[k].release();
         if (c->ring_ev[k]) (void)hipEventDestroy(c->ring_ev[k]);
@@ -298,6 +329,48 @@ int mirsha_bucket_order(const uint32_t* len, uint32_t n, uint32_t* order_out) {
     if (n && (!len || !order_out)) return MIRSHA_EINVAL;
     return bucket_order(len, n, order_out) ? 1 : 0;
 }
+
+int mirsha_bucket_order_device(mirsha_ctx* c, const uint32_t* d_len, uint32_t n, uint32_t min_len, uint32_t max_len,
+                               uint32_t* d_order_out) {
+    if (!c) return MIRSHA_EINVAL;
+    if (min_len > max_len) return fail(c, MIRSHA_EINVAL, "min_len %u > max_len %u", min_len, max_len);
+    const uint32_t bmin = host_blocks(min_len), bmax = host_blocks(max_len);
+    if (bmax - bmin >= MIRSHA_ORDER_MAX_BINS)
+        return fail(c, MIRSHA_ERANGE, "%u block-count bins > %u", bmax - bmin + 1u, MIRSHA_ORDER_MAX_BINS);
+    if (n == 0) return 1;
+    if (!d_len || !d_order_out) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (int rc = use_device(c)) return rc;
+    if (bmin == bmax) {
+        if (int rc = timed_launch(c, kTimerOrder, [&] { return mirsha::launch_order_iota(d_order_out, n, c->stream); }))
+            return rc;
+        return 1;
+    }
+    OrderShape sh;
+    if (int rc = order_buffers(c, n, bmin, bmax, &sh)) return rc;
+    return queue_bucket_order(c, sh, d_len, n, d_order_out);
+}
+
+int mirsha_offsets_device(mirsha_ctx* c, const uint32_t* d_len, uint32_t n, uint64_t* d_off_out) {
+    if (!c) return MIRSHA_EINVAL;
+    if (n == 0) return MIRSHA_OK;
+    if (!d_len || !d_off_out) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (int rc = use_device(c)) return rc;
+    size_t scan_bytes = 0;
+    HIP_TRY(c, mirsha::launch_offsets_scan(nullptr, scan_bytes, nullptr, nullptr, n, c->stream));
+    HIP_TRY(c, c->d_scan.ensure(std::max<size_t>(scan_bytes, 4)));
+    HIP_TRY(c, mirsha::launch_offsets_scan(c->d_scan.p, scan_bytes, d_len, d_off_out, n, c->stream));
+    return MIRSHA_OK;
+}
+
+int mirsha_ctx_set_order_mode(mirsha_ctx* c, int mode) {
+    if (!c) return MIRSHA_EINVAL;
+    if (mode != MIRSHA_ORDER_HOST && mode != MIRSHA_ORDER_DEVICE)
+        return fail(c, MIRSHA_EINVAL, "order mode %d (0 = host, 1 = device)", mode);
+    c->order_mode = mode;
+    return MIRSHA_OK;
+}
+
+int mirsha_ctx_order_mode(const mirsha_ctx* c) { return c ? c->order_mode : MIRSHA_EINVAL; }
 
 int mirsha_synth_mixed_lengths_device(mirsha_ctx* c, uint64_t seed, uint64_t first, uint64_t count,
                                       uint32_t* d_len) {

@@ -425,8 +425,9 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     // hi), total bytes, block-count range, whether the requests are gapless,
     // and the lengths into the metadata block.  Offsets cross PCIe only when
     // the requests are not gapless (else the device rebuilds them by a scan
-    // of the lengths), the bucket order only when block counts differ: 4 B
-    // per request instead of 16 in the common case (the metadata shares the
+    // of the lengths), the bucket order only when block counts differ (and
+    // not with MIRSHA_ORDER_DEVICE: the device then builds it): 4 B per
+    // request instead of 16 in the common case (the metadata shares the
     // link with the request bytes and the digests).
     struct Part {
         uint64_t lo = UINT64_MAX, hi = 0, tot = 0;
@@ -514,9 +515,16 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
             p += len[i];
         }
     }
-    const bool identity = n == 0 || all.bmin == all.bmax || bucket_order(len, n, sord);
-    // bytes of the metadata block that cross PCIe
-    const uint64_t meta_copy = !gapless ? o_end : !identity ? o_ord + 4ull * n : 4ull * n;
+    // MIRSHA_ORDER_DEVICE: a cycle of several block counts gets its bucket
+    // order from the device (queue_bucket_order, with this pass's exact bounds:
+    // the host's order), written into the slot's device order region; neither
+    // the sort nor the order's bytes are the submitting thread's.
+    const bool dev_order = c->order_mode == MIRSHA_ORDER_DEVICE && n && all.bmin != all.bmax &&
+                           all.bmax - all.bmin < MIRSHA_ORDER_MAX_BINS;
+    const bool identity = n == 0 || all.bmin == all.bmax || (!dev_order && bucket_order(len, n, sord));
+    // bytes of the metadata block that cross PCIe (a device order that is not
+    // gapless: the lengths and the offsets, in two copies around the order region)
+    const uint64_t meta_copy = dev_order ? 4ull * n : !gapless ? o_end : !identity ? o_ord + 4ull * n : 4ull * n;
     ph[MIRSHA_PROF_VALIDATE] = ms_since(t0);
     tr[2] = ms_since(t_entry);
     t0 = Clock::now();
@@ -560,6 +568,9 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
         HIP_TRY(c, mirsha::launch_offsets_scan(nullptr, scan_bytes, nullptr, nullptr, n, c->stream));
         HIP_TRY(c, c->d_scan.ensure(std::max<size_t>(scan_bytes, 4)));
     }
+    OrderShape order_shape;
+    if (dev_order)
+        if (int rc = order_buffers(c, n, all.bmin, all.bmax, &order_shape)) return rc;
     if (!from_caller) HIP_TRY(c, sl.stage.ensure(std::max<uint64_t>(bytes, 8)));
     HIP_TRY(c, sl.dev.ensure(d_dig + 32ull * n));
     uint8_t* st = sl.stage.as<uint8_t>();
@@ -589,6 +600,12 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
     }
     tr[4] = ms_since(t_entry);
     // Queue the copies and the kernel (a failure part-way: RingQueued).
+    auto meta_h2d = [&](hipStream_t s) -> int {
+        HIP_TRY(c, hipMemcpyAsync(dv + d_meta, mb, meta_copy, hipMemcpyHostToDevice, s));
+        if (dev_order && !gapless)  // the offsets lie behind the order region, which stays on the device
+            HIP_TRY(c, hipMemcpyAsync(dv + d_meta + o_off, mb + o_off, 8ull * n, hipMemcpyHostToDevice, s));
+        return MIRSHA_OK;
+    };
     auto queue = [&]() -> int {
         if (n) {
             queued.arm();
@@ -596,12 +613,14 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
             // The metadata: behind the request bytes on xin when the kernel
             // stores the digests (one copy stream), else on the kernel stream.
             // (the expectations of a mixed submission travel with it)
-            if (kout) HIP_TRY(c, hipMemcpyAsync(dv + d_meta, mb, meta_copy, hipMemcpyHostToDevice, c->xin));
+            if (kout)
+                if (int rc = meta_h2d(c->xin)) return rc;
             if (kout && sel)
                 if (int rc = expect_h2d(c, sl, *xa, c->xin)) return rc;
             HIP_TRY(c, hipEventRecord(sl.ev_in, c->xin));
             tq[0] = ms_since(t_entry);
-            if (!kout) HIP_TRY(c, hipMemcpyAsync(dv + d_meta, mb, meta_copy, hipMemcpyHostToDevice, c->stream));
+            if (!kout)
+                if (int rc = meta_h2d(c->stream)) return rc;
             if (!kout && sel)
                 if (int rc = expect_h2d(c, sl, *xa, c->stream)) return rc;
             tq[1] = ms_since(t_entry);
@@ -611,6 +630,10 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
             const uint32_t* d_len = reinterpret_cast<const uint32_t*>(dv + d_meta + o_len);
             if (gapless)  // off = exclusive scan of len, on the device (c->d_scan: c->stream's scratch)
                 HIP_TRY(c, mirsha::launch_offsets_scan(c->d_scan.p, scan_bytes, d_len, d_off, n, c->stream));
+            if (dev_order)
+                if (int rc = queue_bucket_order(c, order_shape, d_len, n,
+                                                reinterpret_cast<uint32_t*>(dv + d_meta + o_ord)))
+                    return rc;
             tq[3] = ms_since(t_entry);
             if (int rc = timed_launch(c, 0, [&] {
                     return mirsha::launch_msgs(dv, bytes, d_off, d_len,

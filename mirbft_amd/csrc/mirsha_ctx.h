@@ -20,6 +20,8 @@
 //   mirsha_expect.hip   the select kernels of the mixed submissions
 //   mirsha_commit_ring.hip  a cycle's Commits as a ticket of that ring
 //                       (mirsha_chains_commit_submit*) and their segment kernel
+//   mirsha_order.hip    the kernels of the device-built bucket order
+//                       (mirsha_order.h; queue_bucket_order in mirsha_api.hip)
 //   mirsha_host.cpp     host-only logic, no HIP (dedup scan, packing, the
 //                       expectation / commit plans, a mixed ticket's kept-rows
 //                       walk): unit-tested on the CPU (tests/c)
@@ -48,6 +50,7 @@
 #include "../../include/mirsha.h"
 #include "mirsha_host.h"
 #include "mirsha_device.h"
+#include "mirsha_order.h"
 
 namespace mirsha {
 // mirsha_expect.hip.  Mixed cycles (mirsha_submit_*_expect): compares the
@@ -219,9 +222,10 @@ struct AsyncSlot {
     CommitSlot cm;
 };
 
-constexpr int kKernelTimers = 8;  // timing ids 0-7 (mirsha.h, mirsha_ctx_kernel_time)
+constexpr int kKernelTimers = 9;  // timing ids 0-8 (mirsha.h, mirsha_ctx_kernel_time)
 constexpr int kTimerVerify = 6;
 constexpr int kTimerExpect = 7;
+constexpr int kTimerOrder = 8;
 
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -243,7 +247,11 @@ struct mirsha_ctx {
     uint32_t time_mask = 0xFFFFFFFFu;  // kernels timed while timing is on
     std::string err;
     DevBuf d_arena, d_off, d_len, d_order, d_out, d_idx, d_first, d_out2, d_scratch;
-    DevBuf d_scan;  // scratch of the offsets scan (pipelined gapless calls)
+    DevBuf d_scan;  // scratch of the offsets scan (pipelined gapless calls) and of the order's counts scan
+    // The device-built bucket order (queue_bucket_order): the mode of the arena
+    // submissions, and the counts and their scan, used on c->stream only.
+    int order_mode = MIRSHA_ORDER_HOST;
+    DevBuf d_order_counts;
     // Staged host calls (see "staged host calls" below): a ring of pinned
     // chunks for pageable request bytes, one pinned metadata block (plus small
     // arenas) -> one H2D, and pinned digest staging for small results.
@@ -261,7 +269,7 @@ struct mirsha_ctx {
     // and zeroing per 2^20 requests.
     std::vector<uint32_t> sl_len;
     std::vector<uint64_t> sl_poff;
-    KernelTimer timers[kKernelTimers];  // msgs, lists, gen, chain, fused, overlap, verify, expect
+    KernelTimer timers[kKernelTimers];  // msgs, lists, gen, chain, fused, overlap, verify, expect, order
     // Verify calls (mirsha_verify_*): the expected digests (pinned staging of a
     // pageable caller array, device copy) and the verdict block
     // [count u32, pad | bitmap u64[ceil(n/64)]] on the device and pinned.
@@ -379,6 +387,18 @@ inline uint32_t host_blocks(uint32_t L) { return (uint32_t)(((uint64_t)L + 72u) 
 // Stable sort of message indices by block count, longest first; true if the
 // order is the identity (one bucket).
 bool bucket_order(const uint32_t* len, uint32_t n, uint32_t* order);
+
+// The device-built bucket order (mirsha_order.h) of d_len[0, n) with block
+// counts in [bmin, bmax], bmin < bmax, at most MIRSHA_ORDER_MAX_BINS bins.
+// order_buffers sizes the context's scratch (it may free and so drain the
+// device: before a submission queues anything); queue_bucket_order then only
+// queues, on c->stream: count (timing id 8), scan, scatter (id 8).
+struct OrderShape {
+    uint32_t bmax = 0, bins = 0, chunk = 0, n_chunks = 0;
+    size_t scan_bytes = 0;
+};
+int order_buffers(mirsha_ctx* c, uint32_t n, uint32_t bmin, uint32_t bmax, OrderShape* shape);
+int queue_bucket_order(mirsha_ctx* c, const OrderShape& shape, const uint32_t* d_len, uint32_t n, uint32_t* d_order);
 
 // Orders the context's stream behind the chains' last queued commit submission
 // (no host wait); nothing to do when there was none.

@@ -828,6 +828,31 @@ extern "C" int mirsha_expect_plan(const uint32_t* expect_of, uint32_t m, uint32_
     return MIRSHA_OK;
 }
 
+// The launch shape of the device-built bucket order (mirsha_order.h).  chunk =
+// max(1024, bins rounded up to 64): a wave's chunk holds at least as many
+// messages as its histogram has bins, so the two count arrays (the counts and
+// their scan, bins * n_chunks words each) take
+//   8 bins n_chunks <= 8 bins (n / chunk + 1) <= 8 n + 8 bins <= 8 n + 32768
+// bytes, and a wave walks at least 16 steps per histogram it clears and stores.
+uint32_t mirsha::host::order_chunk(uint32_t bins) { return std::max(1024u, (bins + 63u) & ~63u); }
+
+extern "C" int mirsha_order_plan(uint32_t n, uint32_t min_len, uint32_t max_len, uint32_t* bins_out,
+                                 uint32_t* chunk_out, uint32_t* n_chunks_out, uint64_t* scratch_bytes_out) {
+    if (!bins_out || !chunk_out || !n_chunks_out || !scratch_bytes_out || min_len > max_len) return MIRSHA_EINVAL;
+    const uint32_t bmin = (uint32_t)(((uint64_t)min_len + 72u) >> 6), bmax = (uint32_t)(((uint64_t)max_len + 72u) >> 6);
+    const uint32_t bins = bmax - bmin + 1u;
+    *bins_out = bins;
+    *chunk_out = *n_chunks_out = 0;
+    *scratch_bytes_out = 0;
+    if (bins > MIRSHA_ORDER_MAX_BINS) return MIRSHA_ERANGE;
+    const uint32_t chunk = mirsha::host::order_chunk(bins);
+    const uint32_t n_chunks = (uint32_t)(((uint64_t)n + chunk - 1u) / chunk);
+    *chunk_out = chunk;
+    *n_chunks_out = n_chunks;
+    *scratch_bytes_out = 8ull * bins * n_chunks;
+    return MIRSHA_OK;
+}
+
 // A cycle's commit programme (mirsha_chains_commit) grouped by chain: a
 // validating pass (nothing is written before every op has passed), a count of
 // each chain's entries (null writes dropped), the active chains and their

@@ -126,6 +126,10 @@ bool dedup_rows(const uint32_t* rep, const std::vector<uint32_t>& heads0, const 
 // above n are ignored), one memcpy per run of kept rows, across words too.
 void copy_kept_rows(const uint64_t* has, const uint64_t* mis, uint32_t n, const uint8_t* src, uint8_t* dst);
 
+// Message indices per wave of the device-built bucket order (mirsha_order.h)
+// with `bins` bins: the one rule behind mirsha_order_plan and the launches.
+uint32_t order_chunk(uint32_t bins);
+
 // Copies request which[k] (k < m) to dst + dst_off[k], in parallel.  With
 // `stream` the stores bypass the CPU caches (non-temporal, fenced before
 // return): for page-locked staging a DMA reads next, which then runs at the

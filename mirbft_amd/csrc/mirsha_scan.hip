@@ -12,6 +12,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "mirsha_kernels.h"
+#include "mirsha_order.h"
 
 namespace mirsha {
 
@@ -25,6 +26,14 @@ hipError_t launch_offsets_scan(void* tmp, size_t& tmp_bytes, const uint32_t* len
                                hipStream_t s) {
     auto in = rocprim::make_transform_iterator(len, Widen());
     return rocprim::exclusive_scan(tmp, tmp_bytes, in, off, uint64_t(0), (size_t)n, rocprim::plus<uint64_t>(), s);
+}
+
+// The u32 twin: the per-chunk bin counts of the device-built bucket order
+// (mirsha_order.h) -> each (bin, chunk) cell's first position in the order.
+// The counts add up to the number of messages, a u32.
+hipError_t launch_counts_scan(void* tmp, size_t& tmp_bytes, const uint32_t* in, uint32_t* out, size_t m,
+                              hipStream_t s) {
+    return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, uint32_t(0), m, rocprim::plus<uint32_t>(), s);
 }
 
 }  // namespace mirsha

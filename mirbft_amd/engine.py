@@ -23,6 +23,8 @@ KERNEL_FUSED = 4
 KERNEL_OVERLAP = 5
 KERNEL_VERIFY = 6
 KERNEL_EXPECT = 7
+KERNEL_ORDER = 8
+ORDER_MODES = {"host": _lib.MIRSHA_ORDER_HOST, "device": _lib.MIRSHA_ORDER_DEVICE}
 ASYNC_SLOTS = 4  # submissions in flight per context (mirsha_submit_slices)
 
 # mirsha_pipeline modes (include/mirsha.h)
@@ -335,6 +337,23 @@ class Engine:
 
     def set_variant(self, variant: int) -> None:
         self._check(self._lib.mirsha_ctx_set_variant(self.ctx, int(variant)))
+
+    def set_order_mode(self, mode: str | int) -> None:
+        """Where submit_batch / submit_batch_expect build the bucket order of a
+        cycle of several block counts: "host" (default) or "device"
+        (mirsha_ctx_set_order_mode)."""
+        if isinstance(mode, str):
+            if mode not in ORDER_MODES:
+                raise ValueError(f"order mode {mode!r}: one of {sorted(ORDER_MODES)}")
+            mode = ORDER_MODES[mode]
+        self._check(self._lib.mirsha_ctx_set_order_mode(self.ctx, int(mode)))
+
+    @property
+    def order_mode(self) -> str:
+        m = self._lib.mirsha_ctx_order_mode(self.ctx)
+        if m < 0:
+            self._check(m)
+        return {v: k for k, v in ORDER_MODES.items()}[m]
 
     def set_timing(self, enable: bool) -> None:
         self._check(self._lib.mirsha_ctx_set_timing(self.ctx, 1 if enable else 0))
@@ -653,6 +672,23 @@ class Engine:
                           n: int, d_out: int) -> None:
         self._check(self._lib.mirsha_hash_batch_device(self.ctx, d_arena, arena_len, d_off, d_len, d_order, n, d_out))
 
+    def bucket_order_device(self, d_len: int, n: int, min_len: int, max_len: int, d_order: int) -> bool:
+        """The bucket order of n device-resident lengths into d_order (u32[n]),
+        built on the device, asynchronous on the engine's stream
+        (mirsha_bucket_order_device).  min_len / max_len bound the lengths.
+        True when the order is the identity (one block count): d_order holds it,
+        and None may be passed downstream instead."""
+        rc = self._lib.mirsha_bucket_order_device(self.ctx, d_len or None, int(n), int(min_len), int(max_len),
+                                                  d_order or None)
+        if rc < 0:
+            self._check(rc)
+        return rc == 1
+
+    def offsets_device(self, d_len: int, n: int, d_off: int) -> None:
+        """d_off (u64[n]) = exclusive scan of d_len (u32[n]), on the device,
+        asynchronous on the engine's stream (mirsha_offsets_device)."""
+        self._check(self._lib.mirsha_offsets_device(self.ctx, d_len or None, int(n), d_off or None))
+
     def digest_lists_device(self, d_digests: int, n_digests: int, d_idx: int, d_first: int, n_lists: int,
                             n_entries: int, d_out: int) -> None:
         self._check(self._lib.mirsha_digest_lists_device(self.ctx, d_digests, n_digests, d_idx, d_first, n_lists,
@@ -895,6 +931,19 @@ def bucket_order(length: Sequence[int]) -> tuple[np.ndarray, bool]:
     return order, bool(rc == 1)
 
 
+def order_plan(n: int, min_len: int, max_len: int) -> tuple[int, int, int, int]:
+    """Host-only mirsha_order_plan: (bins, chunk, n_chunks, scratch_bytes) of the
+    device-built bucket order of n lengths within [min_len, max_len]; raises
+    MirshaError (ERANGE) past MIRSHA_ORDER_MAX_BINS bins."""
+    bins, chunk, n_chunks = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+    scratch = ctypes.c_uint64(0)
+    rc = _lib.load().mirsha_order_plan(int(n), int(min_len), int(max_len), ctypes.byref(bins), ctypes.byref(chunk),
+                                       ctypes.byref(n_chunks), ctypes.byref(scratch))
+    if rc != _lib.MIRSHA_OK:
+        raise MirshaError(rc, f"order plan: {bins.value} bins")
+    return bins.value, chunk.value, n_chunks.value, scratch.value
+
+
 def hash_batch_multi(devices: Iterable[int], arena, off, length) -> np.ndarray:
     """Request-range sharding over several devices in one process; host gather."""
     devs = np.ascontiguousarray(list(devices), dtype=np.int32)
@@ -1062,6 +1111,8 @@ __all__ = [
     "KERNEL_OVERLAP",
     "KERNEL_VERIFY",
     "KERNEL_EXPECT",
+    "KERNEL_ORDER",
+    "order_plan",
     "mismatch_indices",
     "PIPELINE_SEQUENTIAL",
     "PIPELINE_FUSED",
