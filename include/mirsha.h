@@ -105,7 +105,8 @@ int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
  * 8 = the kernels of the device-built bucket order (mirsha_bucket_order_device,
  * MIRSHA_ORDER_DEVICE): the count and the scatter kernel, two launches per
  * built order (rocPRIM's scan between them is not timed), or the one identity
- * launch.
+ * launch, 9 = the streams kernel (mirsha_streams_run / _run_device): one
+ * launch per call that has an active stream.
  * set_timing_mask: bit k on = kernel k is timed while timing is enabled
  * (default: all). */
 int mirsha_ctx_set_timing(mirsha_ctx* ctx, int enable);
@@ -754,6 +755,110 @@ int mirsha_chains_commit_submit_device(mirsha_ctx* ctx, mirsha_chains* chains, c
                                        uint32_t n_digests, const uint32_t* op_chain, const uint32_t* op_digest,
                                        uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
                                        uint64_t* ticket_out);
+
+/* ------------------------- streaming hash states: Write / Sum / Reset (a2) */
+/* The reference's hashing boundary is `type Hasher func() hash.Hash`
+ * (processor.go:21): Write any bytes any number of times, Sum(nil) at any
+ * point without disturbing the state, Reset.  Its application log is
+ * application-defined: Log.Apply(*pb.QEntry) and Log.Snap (processor.go:28-31)
+ * may cover sequence numbers, payloads or a serialised entry, not only whole
+ * 32-byte digests as the chains above.  A mirsha_streams holds n_streams such
+ * states on the device, kept across calls: the midstate h[8], the up to 63
+ * bytes of the unfinished block, and the total byte count (u64, so the padded
+ * bit length is 64-bit).  Every stream starts as Hasher().
+ *
+ * One call runs ONE programme of n_ops ops in ONE kernel launch (timing id
+ * 9), one lane per active stream.  Op i acts on stream op_stream[i]
+ * (< n_streams); ops of one stream take effect in op order, streams are
+ * independent.  op_kind[i] is one of the kinds below; op_off[i] / op_len[i]
+ * name the bytes of a WRITE (any byte alignment, any length) and are ignored
+ * for every other kind. */
+typedef struct mirsha_streams mirsha_streams;
+int mirsha_streams_create(mirsha_ctx* ctx, uint32_t n_streams, mirsha_streams** out);
+void mirsha_streams_destroy(mirsha_streams* streams);
+
+#define MIRSHA_STREAM_WRITE 0u     /* Write(arena[op_off[i] .. op_off[i]+op_len[i])) */
+#define MIRSHA_STREAM_SUM 1u       /* Sum(nil) -> next row of values_out; state unchanged (Go's Sum) */
+#define MIRSHA_STREAM_SUM_RESET 2u /* Sum(nil), then Reset() (a checkpoint) */
+#define MIRSHA_STREAM_RESET 3u
+/* At most this many ops a call (a plan entry keeps its kind in 2 bits beside its value row). */
+#define MIRSHA_STREAM_MAX_OPS 0x3FFFFFFFu
+/* Bytes of one exported state (mirsha_streams_export). */
+#define MIRSHA_STREAM_STATE_BYTES 108u
+
+/* Host-only (no device, no context), with the role mirsha_commit_plan has for
+ * the chains: exactly the arrays mirsha_streams_run* sends to the device.
+ *   act_out[k], k < *n_active_out: the streams with at least one entry,
+ *     ascending.  A zero-length write changes nothing and is dropped; a stream
+ *     named only by such writes is not active: the kernel neither reads nor
+ *     writes it.
+ *   efirst_out[0 .. n_active]: stream act_out[k] runs entries
+ *     [efirst_out[k], efirst_out[k+1]) in op order.
+ *   ent_kind_out[e]: the kind in bits 0-1; for SUM / SUM_RESET the row of the
+ *     values output above them: rows count those ops in op order across all
+ *     streams.  ent_off_out[e] / ent_len_out[e]: the bytes of a WRITE entry
+ *     (0 / 0 for every other kind).  pack == 0: the op's own offset (what
+ *     mirsha_streams_run_device sends).  pack != 0: the offset of its bytes
+ *     among the call's packed bytes (what mirsha_streams_run sends, with
+ *     exactly those bytes): every distinct range (op_off, op_len) once, in the
+ *     order of its first entry, without gaps; entries that name one range
+ *     share its bytes (N nodes applying the same log entry).
+ *   *n_values_out: the number of SUM / SUM_RESET ops; *n_bytes_out: pack == 0
+ *     the bytes the write entries name, else the packed bytes.
+ * (On the device the three entry arrays travel as one 16-byte record per
+ * entry: kind, length, offset.)
+ * Capacities: act_out min(n_ops, n_streams), efirst_out one more, the entry
+ * arrays n_ops.  MIRSHA_EINVAL: a NULL array with a non-zero count, a stream
+ * id >= n_streams, an unknown kind, a write with op_off + op_len > arena_len;
+ * then *bad_op_out (if given) is the first offending op, or UINT32_MAX.
+ * MIRSHA_ERANGE: n_ops above MIRSHA_STREAM_MAX_OPS.  MIRSHA_ENOMEM: no host
+ * memory for the per-stream counters. */
+int mirsha_stream_plan(const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                       const uint32_t* op_len, uint32_t n_ops, uint32_t n_streams, uint64_t arena_len, int pack,
+                       uint32_t* act_out, uint32_t* efirst_out, uint32_t* ent_kind_out, uint64_t* ent_off_out,
+                       uint32_t* ent_len_out, uint32_t* n_active_out, uint32_t* n_entries_out, uint32_t* n_values_out,
+                       uint64_t* n_bytes_out, uint32_t* bad_op_out);
+
+/* Runs the programme: one plan, one launch, one synchronisation; synchronous
+ * like mirsha_chains_*.  values_out gets 32 bytes per SUM / SUM_RESET op, in
+ * op order across all streams; *n_values_out is their number.  `arena` is host
+ * memory of any kind (Go memory is fine) and may be sparse: only the bytes the
+ * write ops name cross PCIe, each distinct range once, packed into page-locked
+ * staging of the object with the offsets rewritten (mirsha_stream_plan,
+ * pack).  At most
+ * MIRSHA_MAX_DEVICE_ARENA_BYTES - 256 written bytes a call, else
+ * MIRSHA_ERANGE.  Every check runs on the host before anything is queued:
+ * MIRSHA_EINVAL (the message names the op) for a stream id >= n_streams, an
+ * unknown kind, op_off + op_len > arena_len, or streams of another device; a
+ * failing call leaves every state untouched.  n_ops == 0: MIRSHA_OK,
+ * *n_values_out = 0. */
+int mirsha_streams_run(mirsha_ctx* ctx, mirsha_streams* streams, const uint8_t* arena, uint64_t arena_len,
+                       const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                       const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out);
+/* The same with the arena in device memory (any alignment), read where it lies
+ * on the context's stream, behind whatever was queued there; arena_len at most
+ * MIRSHA_MAX_DEVICE_ARENA_BYTES.  The kernel reads whole aligned 4-byte words:
+ * up to 3 bytes on either side of the arena that share a word with it are
+ * loaded and masked out.  The ops are host arrays and values_out is host
+ * memory, as above. */
+int mirsha_streams_run_device(mirsha_ctx* ctx, mirsha_streams* streams, const uint8_t* d_arena, uint64_t arena_len,
+                              const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                              const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out);
+
+/* The states of streams which[0..k) as MIRSHA_STREAM_STATE_BYTES (108) bytes
+ * each, in the layout of Go 1.14's crypto/sha256 MarshalBinary: the magic
+ * "sha\x03", h[0..7] as big-endian u32, the buffered bytes zero-padded to 64,
+ * the total length as big-endian u64.  With no Go toolchain at hand this
+ * layout is pinned by that description only, not by a round trip through Go.
+ * _import sets the states from such rows (fill = length mod 64) and rejects a
+ * wrong magic (MIRSHA_EINVAL, the message names the row; nothing is changed).
+ * Synchronous; MIRSHA_EINVAL for a stream id >= n_streams.
+ *
+ * Not built here: a ring-ticket form, mirsha_multi_* forms, the C++ mirror,
+ * the Go files, SHA-224. */
+int mirsha_streams_export(mirsha_ctx* ctx, mirsha_streams* streams, const uint32_t* which, uint32_t k, uint8_t* out);
+int mirsha_streams_import(mirsha_ctx* ctx, mirsha_streams* streams, const uint32_t* which, uint32_t k,
+                          const uint8_t* in);
 
 /* ------------------------------------------------- multi-GPU (one process) */
 /* Shards the n requests by contiguous range across ndev devices (balanced by

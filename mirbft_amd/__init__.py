@@ -7,16 +7,25 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 """
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
-from .engine import (CheckpointChains, CommitTicket, Engine, ExpectTicket, MultiEngine, SliceArrays, Ticket, bucket_order,
-                     commit_plan, commit_seg_plan, dedup_plan, dedup_rows, device_count, expect_bitmap, expect_plan, hash_batch_multi,
-                     mismatch_indices, order_plan)
+from .engine import (STREAM_RESET, STREAM_SUM, STREAM_SUM_RESET, STREAM_WRITE, CheckpointChains, CommitTicket, Engine,
+                     ExpectTicket, HashStreams, MultiEngine, SliceArrays, StreamHasher, Ticket, bucket_order, commit_plan,
+                     commit_seg_plan, dedup_plan, dedup_rows, device_count, expect_bitmap, expect_plan, hash_batch_multi,
+                     mismatch_indices, order_plan, stream_plan)
 from .processor import (ActionResults, Actions, Checkpoint, CheckpointResult, Commit, CommitBatch, DeviceLog, GpuHash,
-                        HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, commit_programme,
-                        gpu_hasher)
+                        HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, StreamLog,
+                        commit_programme, gpu_hasher)
 
 __all__ = [
     "Engine",
     "CheckpointChains",
+    "HashStreams",
+    "StreamHasher",
+    "StreamLog",
+    "stream_plan",
+    "STREAM_WRITE",
+    "STREAM_SUM",
+    "STREAM_SUM_RESET",
+    "STREAM_RESET",
     "SliceArrays",
     "Ticket",
     "ExpectTicket",

@@ -22,8 +22,10 @@
 //                       (mirsha_chains_commit_submit*) and their segment kernel
 //   mirsha_order.hip    the kernels of the device-built bucket order
 //                       (mirsha_order.h; queue_bucket_order in mirsha_api.hip)
+//   mirsha_streams.hip  streaming hash states over any bytes (mirsha_streams_*)
+//                       and their kernel (mirsha_streams.h)
 //   mirsha_host.cpp     host-only logic, no HIP (dedup scan, packing, the
-//                       expectation / commit plans, a mixed ticket's kept-rows
+//                       expectation / commit / stream plans, a mixed ticket's kept-rows
 //                       walk): unit-tested on the CPU (tests/c)
 //   mirsha_multi.hip    the multi-device drop-in (mirsha_multi_*)
 //
@@ -222,10 +224,11 @@ struct AsyncSlot {
     CommitSlot cm;
 };
 
-constexpr int kKernelTimers = 9;  // timing ids 0-8 (mirsha.h, mirsha_ctx_kernel_time)
+constexpr int kKernelTimers = 10;  // timing ids 0-9 (mirsha.h, mirsha_ctx_kernel_time)
 constexpr int kTimerVerify = 6;
 constexpr int kTimerExpect = 7;
 constexpr int kTimerOrder = 8;
+constexpr int kTimerStreams = 9;
 
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
@@ -269,7 +272,7 @@ struct mirsha_ctx {
     // and zeroing per 2^20 requests.
     std::vector<uint32_t> sl_len;
     std::vector<uint64_t> sl_poff;
-    KernelTimer timers[kKernelTimers];  // msgs, lists, gen, chain, fused, overlap, verify, expect, order
+    KernelTimer timers[kKernelTimers];  // msgs, lists, gen, chain, fused, overlap, verify, expect, order, streams
     // Verify calls (mirsha_verify_*): the expected digests (pinned staging of a
     // pageable caller array, device copy) and the verdict block
     // [count u32, pad | bitmap u64[ceil(n/64)]] on the device and pinned.

@@ -957,3 +957,115 @@ extern "C" int mirsha_commit_seg_plan(const uint32_t* op_chain, const uint32_t* 
     *n_seg_out = ns;
     return MIRSHA_OK;
 }
+
+// Where the bytes of each write entry lie among a call's packed bytes: every
+// distinct range (offset, length) once, in the order of its first entry, no
+// gaps; an entry that names a range again shares its bytes (N nodes applying
+// the same log entry).
+uint64_t mirsha::host::stream_pack_offsets(const uint64_t* off, const uint32_t* len, uint32_t entries,
+                                           uint64_t* poff_out) {
+    struct Key {
+        uint64_t off;
+        uint32_t len;
+        bool operator==(const Key& o) const { return off == o.off && len == o.len; }
+    };
+    struct KeyHash {
+        size_t operator()(const Key& k) const {
+            return (size_t)((k.off * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)k.len * 0xC2B2AE3D27D4EB4Full));
+        }
+    };
+    std::unordered_map<Key, uint64_t, KeyHash> seen;
+    uint64_t bytes = 0;
+    for (uint32_t e = 0; e < entries; e++) {
+        if (!len[e]) {
+            poff_out[e] = 0;
+            continue;
+        }
+        const auto it = seen.emplace(Key{off[e], len[e]}, bytes);  // before poff_out[e] is written: may alias off
+        poff_out[e] = it.first->second;
+        if (it.second) bytes += len[e];
+    }
+    return bytes;
+}
+
+// A call's stream programme (mirsha_streams_run) grouped by stream, as
+// mirsha_commit_plan groups a commit programme by chain: a validating pass
+// (nothing is written before every op has passed), a count of each stream's
+// entries (zero-length writes dropped), the active streams and their ranges,
+// a stable scatter in op order.  Value rows count the SUM / SUM_RESET ops in
+// op order across all streams.  With `pack` the write entries' offsets are
+// those of the packed bytes (stream_pack_offsets).
+extern "C" int mirsha_stream_plan(const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                                  const uint32_t* op_len, uint32_t n_ops, uint32_t n_streams, uint64_t arena_len,
+                                  int pack, uint32_t* act_out, uint32_t* efirst_out, uint32_t* ent_kind_out,
+                                  uint64_t* ent_off_out, uint32_t* ent_len_out, uint32_t* n_active_out,
+                                  uint32_t* n_entries_out, uint32_t* n_values_out, uint64_t* n_bytes_out,
+                                  uint32_t* bad_op_out) {
+    if (bad_op_out) *bad_op_out = UINT32_MAX;
+    if (!n_active_out || !n_entries_out || !n_values_out || !n_bytes_out) return MIRSHA_EINVAL;
+    *n_active_out = *n_entries_out = *n_values_out = 0;
+    *n_bytes_out = 0;
+    if (n_ops > MIRSHA_STREAM_MAX_OPS) return MIRSHA_ERANGE;
+    if (n_ops == 0) {
+        if (efirst_out) efirst_out[0] = 0;
+        return MIRSHA_OK;
+    }
+    if (!op_stream || !op_kind) return MIRSHA_EINVAL;
+    bool writes = false;
+    for (uint32_t i = 0; i < n_ops && !writes; i++) writes = op_kind[i] == MIRSHA_STREAM_WRITE;
+    if (writes && (!op_off || !op_len)) return MIRSHA_EINVAL;
+    for (uint32_t i = 0; i < n_ops; i++) {
+        bool ok = op_stream[i] < n_streams && op_kind[i] <= MIRSHA_STREAM_RESET;
+        if (ok && op_kind[i] == MIRSHA_STREAM_WRITE)
+            ok = op_off[i] <= arena_len && op_len[i] <= arena_len - op_off[i];
+        if (!ok) {
+            if (bad_op_out) *bad_op_out = i;
+            return MIRSHA_EINVAL;
+        }
+    }
+    if (!act_out || !efirst_out || !ent_kind_out || !ent_off_out || !ent_len_out) return MIRSHA_EINVAL;
+    auto dropped = [&](uint32_t i) { return op_kind[i] == MIRSHA_STREAM_WRITE && op_len[i] == 0; };
+    std::vector<uint32_t> at;  // entries of stream s, then where its next entry goes
+    try {
+        at.assign((size_t)n_streams, 0);
+    } catch (const std::bad_alloc&) {
+        return MIRSHA_ENOMEM;
+    }
+    for (uint32_t i = 0; i < n_ops; i++)
+        if (!dropped(i)) at[op_stream[i]]++;
+    uint32_t na = 0, total = 0;
+    efirst_out[0] = 0;
+    for (uint32_t s = 0; s < n_streams; s++) {
+        const uint32_t m = at[s];
+        at[s] = total;
+        if (!m) continue;
+        act_out[na++] = s;
+        total += m;
+        efirst_out[na] = total;
+    }
+    uint32_t rows = 0;
+    for (uint32_t i = 0; i < n_ops; i++) {
+        if (dropped(i)) continue;
+        const uint32_t e = at[op_stream[i]]++;
+        const uint32_t k = op_kind[i];
+        const bool sum = k == MIRSHA_STREAM_SUM || k == MIRSHA_STREAM_SUM_RESET;
+        ent_kind_out[e] = k | (sum ? rows++ << 2 : 0u);
+        ent_off_out[e] = k == MIRSHA_STREAM_WRITE ? op_off[i] : 0u;
+        ent_len_out[e] = k == MIRSHA_STREAM_WRITE ? op_len[i] : 0u;
+    }
+    uint64_t bytes = 0;
+    if (pack) {
+        try {
+            bytes = mirsha::host::stream_pack_offsets(ent_off_out, ent_len_out, total, ent_off_out);
+        } catch (const std::bad_alloc&) {
+            return MIRSHA_ENOMEM;
+        }
+    } else {
+        for (uint32_t e = 0; e < total; e++) bytes += ent_len_out[e];
+    }
+    *n_active_out = na;
+    *n_entries_out = total;
+    *n_values_out = rows;
+    *n_bytes_out = bytes;
+    return MIRSHA_OK;
+}

@@ -24,6 +24,12 @@ KERNEL_OVERLAP = 5
 KERNEL_VERIFY = 6
 KERNEL_EXPECT = 7
 KERNEL_ORDER = 8
+KERNEL_STREAMS = 9
+# op kinds of a stream programme (mirsha_streams_run)
+STREAM_WRITE = _lib.MIRSHA_STREAM_WRITE
+STREAM_SUM = _lib.MIRSHA_STREAM_SUM
+STREAM_SUM_RESET = _lib.MIRSHA_STREAM_SUM_RESET
+STREAM_RESET = _lib.MIRSHA_STREAM_RESET
 ORDER_MODES = {"host": _lib.MIRSHA_ORDER_HOST, "device": _lib.MIRSHA_ORDER_DEVICE}
 ASYNC_SLOTS = 4  # submissions in flight per context (mirsha_submit_slices)
 
@@ -919,6 +925,207 @@ class CheckpointChains:
             self.close()
         except Exception:
             pass
+
+
+def _stream_ops(ops) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """A stream programme as the four op arrays of mirsha_streams_run: either
+    those arrays themselves, ``(op_stream, op_kind, op_off, op_len)``, or a
+    sequence of ``(stream, STREAM_WRITE, off, len)`` / ``(stream, kind)`` tuples."""
+    if isinstance(ops, tuple) and len(ops) == 4 and all(isinstance(a, np.ndarray) for a in ops):
+        cols = ops
+    else:
+        rows = [tuple(op) + (0, 0) * (len(op) == 2) for op in ops]
+        if any(len(r) != 4 for r in rows):
+            raise ValueError("an op is (stream, kind) or (stream, kind, off, len)")
+        cols = tuple(zip(*rows)) if rows else ((), (), (), ())
+    os_, ok, oo, ol = (np.ascontiguousarray(c, dtype=t).reshape(-1)
+                       for c, t in zip(cols, (np.uint32, np.uint32, np.uint64, np.uint32)))
+    if not os_.size == ok.size == oo.size == ol.size:
+        raise ValueError("one stream, kind, offset and length per op")
+    return os_, ok, oo, ol
+
+
+def stream_plan(ops, n_streams: int, arena_len: int, pack: bool = False):
+    """Host-only mirsha_stream_plan: the arrays ``HashStreams.run`` (pack=True)
+    / ``run_device`` (pack=False) send to the device.  Returns (act, efirst,
+    ent_kind, ent_off, ent_len, n_values, n_bytes): the active streams
+    (ascending), their entry ranges in op order with zero-length writes
+    dropped, per entry the kind in bits 0-1 (and, for a sum, the values row
+    above them), the write's offset and length, the number of sums and the
+    bytes the writes name.  pack=True: offsets into the packed bytes -- every
+    distinct (off, len) range once, in the order of its first entry, without
+    gaps -- and their size as n_bytes."""
+    os_, ok, oo, ol = _stream_ops(ops)
+    cap = min(os_.size, int(n_streams))
+    act = np.zeros(cap, dtype=np.uint32)
+    efirst = np.zeros(cap + 1, dtype=np.uint32)
+    kind = np.zeros(os_.size, dtype=np.uint32)
+    off = np.zeros(os_.size, dtype=np.uint64)
+    ln = np.zeros(os_.size, dtype=np.uint32)
+    na, ne, nv, bad = (ctypes.c_uint32(0) for _ in range(4))
+    nb = ctypes.c_uint64(0)
+    rc = _lib.load().mirsha_stream_plan(_ptr(os_), _ptr(ok), _ptr(oo), _ptr(ol), os_.size, int(n_streams),
+                                        int(arena_len), 1 if pack else 0, _ptr(act), efirst.ctypes.data, _ptr(kind),
+                                        _ptr(off), _ptr(ln), ctypes.byref(na), ctypes.byref(ne), ctypes.byref(nv),
+                                        ctypes.byref(nb), ctypes.byref(bad))
+    if rc != _lib.MIRSHA_OK:
+        err = MirshaError(rc, f"stream plan: op {bad.value}" if bad.value != 0xFFFFFFFF else "stream plan: arguments")
+        err.bad_op = None if bad.value == 0xFFFFFFFF else bad.value
+        raise err
+    return (act[:na.value], efirst[:na.value + 1], kind[:ne.value], off[:ne.value], ln[:ne.value], nv.value,
+            nb.value)
+
+
+class HashStreams:
+    """Streaming SHA-256 states on the device (mirsha_streams_*): n hashers in
+    the reference's own shape, ``type Hasher func() hash.Hash``
+    (processor.go:21) -- Write any bytes any number of times, Sum at any point
+    without disturbing the state, Reset -- whose midstate, unfinished block and
+    length stay on the device across calls.  ``run`` is ONE programme over any
+    number of streams in ONE launch; ``hasher()`` / ``flush`` is the hash.Hash
+    form on top of it.  ``bytes_sent`` counts the bytes of the distinct ranges
+    the write ops of each ``run`` named (what crossed PCIe); ``runs`` the calls."""
+
+    def __init__(self, engine: Engine, n_streams: int):
+        self._engine = engine
+        self._lib = engine._lib
+        h = ctypes.c_void_p()
+        engine._check(self._lib.mirsha_streams_create(engine.ctx, int(n_streams), ctypes.byref(h)))
+        self.handle = h
+        self.n = int(n_streams)
+        self.bytes_sent = 0
+        self.runs = 0
+        self._free = list(range(self.n - 1, -1, -1))
+
+    def run(self, ops, arena=b"") -> np.ndarray:
+        """Runs the programme ``ops`` (see ``_stream_ops``) over host bytes:
+        a write op names ``arena[off:off+len]``.  Returns the (k, 32) uint8
+        digests of its k STREAM_SUM / STREAM_SUM_RESET ops, in op order."""
+        a = _as_u8(arena)
+        return self._run(self._lib.mirsha_streams_run, _ptr(a), a.size, ops)
+
+    def run_device(self, ops, d_arena: int, arena_len: int) -> np.ndarray:
+        """run() with the arena in device memory (a raw device address, any
+        alignment), read where it lies behind whatever is queued on the
+        engine's stream."""
+        return self._run(self._lib.mirsha_streams_run_device, int(d_arena) or None, int(arena_len), ops)
+
+    def _run(self, call, arena, arena_len: int, ops) -> np.ndarray:
+        os_, ok, oo, ol = _stream_ops(ops)
+        sums = (ok == _lib.MIRSHA_STREAM_SUM) | (ok == _lib.MIRSHA_STREAM_SUM_RESET)
+        out = np.empty((int(np.count_nonzero(sums)), 32), dtype=np.uint8)
+        k = ctypes.c_uint32(0)
+        self._engine._check(call(self._engine.ctx, self.handle, arena, arena_len, _ptr(os_), _ptr(ok), _ptr(oo),
+                                 _ptr(ol), os_.size, _ptr(out), ctypes.byref(k)))
+        if k.value != out.shape[0]:
+            raise MirshaError(_lib.MIRSHA_EHIP, f"streams: {k.value} values for {out.shape[0]} sums")
+        if call is self._lib.mirsha_streams_run:
+            w = (ok == _lib.MIRSHA_STREAM_WRITE) & (ol != 0)
+            ranges = np.unique(np.stack([oo[w], ol[w].astype(np.uint64)]), axis=1)
+            self.bytes_sent += int(ranges[1].sum())
+        self.runs += 1
+        return out
+
+    def export_state(self, which) -> np.ndarray:
+        """The states of streams ``which`` as (k, 108) uint8 rows in the layout
+        of Go 1.14's crypto/sha256 MarshalBinary (mirsha_streams_export)."""
+        w = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        out = np.empty((w.size, _lib.MIRSHA_STREAM_STATE_BYTES), dtype=np.uint8)
+        if w.size:
+            self._engine._check(self._lib.mirsha_streams_export(self._engine.ctx, self.handle, _ptr(w), w.size,
+                                                                _ptr(out)))
+        return out
+
+    def import_state(self, which, states) -> None:
+        """Sets streams ``which`` from such rows (mirsha_streams_import); a row
+        that does not begin with the magic is refused and nothing changes."""
+        w = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
+        if isinstance(states, (bytes, bytearray, memoryview)):
+            states = np.frombuffer(bytes(states), dtype=np.uint8)
+        rows = np.ascontiguousarray(states, dtype=np.uint8).reshape(-1, _lib.MIRSHA_STREAM_STATE_BYTES)
+        if rows.shape[0] != w.size:
+            raise ValueError("one 108-byte state per stream")
+        if w.size:
+            self._engine._check(self._lib.mirsha_streams_import(self._engine.ctx, self.handle, _ptr(w), w.size,
+                                                                _ptr(rows)))
+
+    # ------------------------------------------------------- hash.Hash form
+    def hasher(self) -> "StreamHasher":
+        """A hash.Hash-shaped object bound to a free stream (``close()`` gives
+        the stream back).  Its first flush starts with a Reset, so it is
+        Hasher() whatever the stream held."""
+        if not self._free:
+            raise MirshaError(_lib.MIRSHA_ERANGE, f"all {self.n} streams are in use")
+        return StreamHasher(self, self._free.pop())
+
+    def flush(self, hashers, sums: bool = True) -> list:
+        """Sends the pending Resets and writes of ``hashers`` -- and with
+        ``sums`` one Sum each -- in ONE ``run``: the batched use.  Returns the
+        digests (bytes) in the order of ``hashers``, or [] without sums."""
+        ops, parts, at = [], [], 0
+        for hs in hashers:
+            if hs._streams is not self or hs.stream is None:
+                raise ValueError("a hasher of another HashStreams, or a closed one")
+            if hs._reset:
+                ops.append((hs.stream, _lib.MIRSHA_STREAM_RESET, 0, 0))
+            size = sum(len(p) for p in hs._pending)
+            if size:
+                ops.append((hs.stream, _lib.MIRSHA_STREAM_WRITE, at, size))
+                parts.extend(hs._pending)
+                at += size
+            if sums:
+                ops.append((hs.stream, _lib.MIRSHA_STREAM_SUM, 0, 0))
+        out = self.run(ops, b"".join(parts)) if ops else np.empty((0, 32), dtype=np.uint8)
+        for hs in hashers:  # sent: only now, a refused run leaves them pending
+            hs._pending, hs._reset = [], False
+        return [row.tobytes() for row in out]
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self._lib.mirsha_streams_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class StreamHasher:
+    """hash.Hash (Write / Sum / Reset / Size / BlockSize) over one stream of a
+    ``HashStreams``: ``write`` buffers on the host, ``sum`` sends only the
+    bytes not sent yet plus a Sum (the state stays on the device, so a hasher
+    summed after every write sends each byte once), ``reset`` is sent with the
+    next flush."""
+
+    size = 32
+    block_size = 64
+
+    def __init__(self, streams: HashStreams, stream: int):
+        self._streams = streams
+        self.stream = stream
+        self._pending: list[bytes] = []
+        self._reset = True
+
+    def write(self, data) -> int:
+        if self.stream is None:
+            raise ValueError("write to a closed hasher")
+        if len(data):
+            self._pending.append(bytes(data))
+        return len(data)
+
+    def sum(self, b: bytes = b"") -> bytes:
+        return bytes(b) + self._streams.flush([self])[0]
+
+    def reset(self) -> None:
+        self._pending, self._reset = [], True
+
+    def close(self) -> None:
+        if self.stream is not None:
+            self._streams._free.append(self.stream)
+            self.stream = None
+            self._pending = []
 
 
 def bucket_order(length: Sequence[int]) -> tuple[np.ndarray, bool]:

@@ -66,7 +66,7 @@ from typing import Any, Callable, Optional
 import numpy as np
 
 from ._lib import MIRSHA_COMMIT_CHECKPOINT, MIRSHA_NULL_INDEX
-from .engine import CheckpointChains, Engine
+from .engine import STREAM_SUM_RESET, STREAM_WRITE, CheckpointChains, Engine, HashStreams
 
 
 @dataclass(eq=False)
@@ -208,6 +208,69 @@ class DeviceLog:
 
     def close(self) -> None:
         self.chains.close()
+
+
+def batch_digests(batch) -> list:
+    """``StreamLog``'s default ``entry_data``: the batch's non-null request
+    digests, what the testengine log writes (recorder.go:222-223)."""
+    out = []
+    for d in batch.digests:
+        if d is None or len(d) == 0:
+            continue
+        if len(d) != 32:
+            raise ValueError(f"a request digest of {len(d)} bytes")
+        out.append(bytes(d))
+    return out
+
+
+class StreamLog:
+    """``DeviceLog``'s interface over ``HashStreams``: an application log whose
+    ``Apply`` writes ANY bytes (Log.Apply(*pb.QEntry) / Log.Snap are
+    application-defined, processor.go:28-31), e.g. sequence numbers, payloads
+    or a serialised entry.  ``entry_data(batch) -> list[bytes]`` is what Apply
+    writes for a committed batch; the default writes its non-null request
+    digests, which reproduces ``DeviceLog``'s checkpoint values.  A checkpoint
+    is Sum-then-Reset.  One cycle's ``actions.commits`` is ONE
+    ``HashStreams.run``: per commit n_nodes consecutive ops (node 0 first), so
+    ``values`` is (checkpoints, n_nodes, 32) as ``DeviceLog``'s.  Every node's
+    write op names the same range of the cycle's arena, and ``run`` sends each
+    distinct range once: a cycle's bytes cross PCIe once, whatever n_nodes is.
+    ``DeviceLog`` stays the log for digest-only applications."""
+
+    def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, entry_data=None, streams=None):
+        if not 0 <= node < n_nodes:
+            raise ValueError(f"node {node} of {n_nodes}")
+        self._engine = engine
+        self.n_nodes, self.node = int(n_nodes), int(node)
+        self.entry_data = entry_data if entry_data is not None else batch_digests
+        self.streams = streams if streams is not None else HashStreams(engine, self.n_nodes)
+        self.values = np.empty((0, self.n_nodes, 32), dtype=np.uint8)
+
+    def cycle_programme(self, commits):
+        """Host-only: (ops, arena) of one cycle for ``HashStreams.run``."""
+        kinds, offs, lens, parts, at = [], [], [], [], 0
+        for k, commit in enumerate(commits):
+            if (commit.batch is None) == (commit.checkpoint is None):
+                raise ValueError(f"commits[{k}]: exactly one of batch and checkpoint must be set")
+            if commit.checkpoint is not None:
+                kinds.append(STREAM_SUM_RESET), offs.append(0), lens.append(0)
+                continue
+            data = b"".join(bytes(d) for d in self.entry_data(commit.batch))
+            kinds.append(STREAM_WRITE), offs.append(at), lens.append(len(data))
+            parts.append(data)
+            at += len(data)
+        n = self.n_nodes
+        ops = (np.tile(np.arange(n, dtype=np.uint32), len(kinds)), np.repeat(np.asarray(kinds, dtype=np.uint32), n),
+               np.repeat(np.asarray(offs, dtype=np.uint64), n), np.repeat(np.asarray(lens, dtype=np.uint32), n))
+        return ops, b"".join(parts)
+
+    def commit_cycle(self, commits) -> list:
+        ops, arena = self.cycle_programme(commits)
+        self.values = self.streams.run(ops, arena).reshape(-1, self.n_nodes, 32)
+        return [v.tobytes() for v in self.values[:, self.node]]
+
+    def close(self) -> None:
+        self.streams.close()
 
 
 class GpuHash:
