@@ -105,8 +105,9 @@ int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
  * 8 = the kernels of the device-built bucket order (mirsha_bucket_order_device,
  * MIRSHA_ORDER_DEVICE): the count and the scatter kernel, two launches per
  * built order (rocPRIM's scan between them is not timed), or the one identity
- * launch, 9 = the streams kernel (mirsha_streams_run / _run_device): one
- * launch per call that has an active stream.
+ * launch, 9 = the streams kernels (mirsha_streams_run / _run_device, and the
+ * segment kernel of mirsha_streams_submit / _submit_device): one launch per
+ * call that has an active stream.
  * set_timing_mask: bit k on = kernel k is timed while timing is enabled
  * (default: all). */
 int mirsha_ctx_set_timing(mirsha_ctx* ctx, int enable);
@@ -854,11 +855,99 @@ int mirsha_streams_run_device(mirsha_ctx* ctx, mirsha_streams* streams, const ui
  * wrong magic (MIRSHA_EINVAL, the message names the row; nothing is changed).
  * Synchronous; MIRSHA_EINVAL for a stream id >= n_streams.
  *
- * Not built here: a ring-ticket form, mirsha_multi_* forms, the C++ mirror,
- * the Go files, SHA-224. */
+ * On an object with a stream ticket in flight (mirsha_streams_submit, below)
+ * _run*, _export and _import first make the context's stream wait for it.
+ *
+ * Not built here: mirsha_multi_* forms, the C++ mirror, the Go files,
+ * SHA-224. */
 int mirsha_streams_export(mirsha_ctx* ctx, mirsha_streams* streams, const uint32_t* which, uint32_t k, uint8_t* out);
 int mirsha_streams_import(mirsha_ctx* ctx, mirsha_streams* streams, const uint32_t* which, uint32_t k,
                           const uint8_t* in);
+
+/* ----------------------- a stream programme on the asynchronous ring (a2.1) */
+/* The ring form of mirsha_streams_run, as mirsha_chains_commit_submit is the
+ * ring form of mirsha_chains_commit: the programme is queued, the call
+ * returns, and the values are complete when the ticket retires.
+ *
+ * Behind a SUM_RESET or a RESET a stream restarts from Hasher(), so the
+ * stretches of one stream between them are independent hashes.  The ring form
+ * cuts each active stream's entries after every such entry into SEGMENTS and
+ * runs one lane per segment: a stream with k Sum-then-Reset ops costs its
+ * longest stretch, not their sum.  A plain SUM leaves the state as it was and
+ * does not cut. */
+#define MIRSHA_STREAM_SEG_FIRST 1u /* the stream's first segment: starts from the stored row */
+#define MIRSHA_STREAM_SEG_LAST 2u  /* holds the stream's final entry: stores the state it ends in */
+
+/* Host-only, like mirsha_stream_plan, whose output it is built on (same
+ * checks, codes and *bad_op_out; the three entry arrays, *n_active_out,
+ * *n_entries_out, *n_values_out and *n_bytes_out are that plan's, unchanged,
+ * for either value of `pack`).  Segment s, s < *n_seg_out:
+ *   seg_stream_out[s]: its stream;
+ *   entries [sfirst_out[s], sfirst_out[s+1]) of the entry arrays,
+ *     sfirst_out[0] = 0, sfirst_out[n_seg] = *n_entries_out;
+ *   seg_flags_out[s]: MIRSHA_STREAM_SEG_FIRST starts from the stream's stored
+ *     row; every other segment starts from Hasher(): H0, count 0, an all-zero
+ *     block.  MIRSHA_STREAM_SEG_LAST stores the state it ends in as the
+ *     stream's.
+ * A segment ends with a SUM_RESET or RESET entry or with the stream's final
+ * entry: a stream whose entries end with one of the two gets no empty segment
+ * behind it (its last segment ends in that entry and stores Hasher()).
+ * Segments are stream-major (streams ascending), in op order within a stream.
+ * *n_seg_out = active streams + SUM_RESET / RESET entries that are not their
+ * stream's final entry.  The writes of a segment that ends in a RESET without
+ * a sum in it are dead work; they are not dropped.
+ * Capacities: seg_stream_out and seg_flags_out n_ops entries, sfirst_out one
+ * more, the entry arrays n_ops. */
+int mirsha_stream_seg_plan(const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                           const uint32_t* op_len, uint32_t n_ops, uint32_t n_streams, uint64_t arena_len, int pack,
+                           uint32_t* seg_stream_out, uint32_t* sfirst_out, uint32_t* seg_flags_out,
+                           uint32_t* ent_kind_out, uint64_t* ent_off_out, uint32_t* ent_len_out, uint32_t* n_seg_out,
+                           uint32_t* n_active_out, uint32_t* n_entries_out, uint32_t* n_values_out,
+                           uint64_t* n_bytes_out, uint32_t* bad_op_out);
+
+/* mirsha_streams_run as a ring submission: arguments, checks, error codes,
+ * messages and the size limit are that call's.  Before the call returns every
+ * check and the plan have run on the host, *n_values_out is written, and the
+ * op arrays and every distinct written range of the (host) arena are copied
+ * into the ring slot's page-locked block: the caller may reuse them at once.
+ * The call takes the context's next ticket and ring slot like mirsha_submit_*
+ * and mirsha_chains_commit_submit; the ticket is retired by mirsha_wait /
+ * mirsha_poll in ticket order, mixed freely with hashing and commit tickets,
+ * and a fifth submission retires the oldest.  values_out (32 bytes per SUM /
+ * SUM_RESET op, op order) must stay valid until the ticket retires and is
+ * complete then.  A validation failure queues nothing, consumes no ticket and
+ * leaves every state untouched.  A programme without an active stream
+ * (n_ops == 0, or zero-length writes only): a valid ticket, nothing launched.
+ *
+ * The device work runs on the context's commit stream (the one of
+ * mirsha_chains_commit_submit, created at the first such call), so commit and
+ * stream tickets run in submission order among themselves, beside the hashing
+ * on the context's stream: one H2D copy of the slot's block, one launch of the
+ * segment kernel (timing id 9), the slot's completion event.  When a stream's
+ * first and last segment fall into different waves, a device-to-device copy of
+ * the state rows precedes the launch (the first segments read that copy;
+ * without it a last segment's store could overtake the first segment's load).
+ * The kernel stores the values straight into a page-locked, 16-byte aligned
+ * values_out, otherwise into page-locked rows of the slot that are copied out
+ * at retirement: there is no D2H copy.  mirsha_streams_run* / _export /
+ * _import on an object with a ticket in flight first make the context's
+ * stream wait for it, so both forms mix on one object without the caller
+ * waiting; mirsha_streams_destroy waits for the object's last queued ticket.
+ * mirsha_ctx_host_profile of a retired stream ticket: validate = checks and
+ * plan, pack = the staging copy, device = queued -> complete, scatter = the
+ * values' copy. */
+int mirsha_streams_submit(mirsha_ctx* ctx, mirsha_streams* streams, const uint8_t* arena, uint64_t arena_len,
+                          const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                          const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
+                          uint64_t* ticket_out);
+/* The same with the arena in device memory (any alignment).  The commit stream
+ * waits on an event recorded on the context's stream at submission, so the
+ * arena is read behind whatever was queued there (e.g. the hashing that
+ * writes it); it must stay intact until the ticket retires. */
+int mirsha_streams_submit_device(mirsha_ctx* ctx, mirsha_streams* streams, const uint8_t* d_arena, uint64_t arena_len,
+                                 const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                                 const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
+                                 uint64_t* ticket_out);
 
 /* ------------------------------------------------- multi-GPU (one process) */
 /* Shards the n requests by contiguous range across ndev devices (balanced by

@@ -8,9 +8,9 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
 from .engine import (STREAM_RESET, STREAM_SUM, STREAM_SUM_RESET, STREAM_WRITE, CheckpointChains, CommitTicket, Engine,
-                     ExpectTicket, HashStreams, MultiEngine, SliceArrays, StreamHasher, Ticket, bucket_order, commit_plan,
+                     ExpectTicket, HashStreams, MultiEngine, SliceArrays, StreamHasher, StreamTicket, Ticket, bucket_order, commit_plan,
                      commit_seg_plan, dedup_plan, dedup_rows, device_count, expect_bitmap, expect_plan, hash_batch_multi,
-                     mismatch_indices, order_plan, stream_plan)
+                     mismatch_indices, order_plan, stream_plan, stream_seg_plan)
 from .processor import (ActionResults, Actions, Checkpoint, CheckpointResult, Commit, CommitBatch, DeviceLog, GpuHash,
                         HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, StreamLog,
                         commit_programme, gpu_hasher)
@@ -22,6 +22,7 @@ __all__ = [
     "StreamHasher",
     "StreamLog",
     "stream_plan",
+    "stream_seg_plan",
     "STREAM_WRITE",
     "STREAM_SUM",
     "STREAM_SUM_RESET",
@@ -30,6 +31,7 @@ __all__ = [
     "Ticket",
     "ExpectTicket",
     "CommitTicket",
+    "StreamTicket",
     "dedup_plan",
     "dedup_rows",
     "expect_plan",

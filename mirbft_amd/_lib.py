@@ -31,6 +31,8 @@ MIRSHA_STREAM_SUM_RESET = 2
 MIRSHA_STREAM_RESET = 3
 MIRSHA_STREAM_MAX_OPS = 0x3FFFFFFF
 MIRSHA_STREAM_STATE_BYTES = 108
+MIRSHA_STREAM_SEG_FIRST = 1
+MIRSHA_STREAM_SEG_LAST = 2
 MIRSHA_MAX_MESSAGE_BYTES = 0xFFFFFF00
 MIRSHA_MAX_DEVICE_ARENA_BYTES = 0xFFFFFF00
 MIRSHA_SUBMIT_DEDUP = 1
@@ -200,6 +202,21 @@ SIGNATURES = {
     ),
     "mirsha_streams_export": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "mirsha_streams_import": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "mirsha_stream_seg_plan": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_uint32, c_uint64, c_int, c_void_p, c_void_p, c_void_p,
+         c_void_p, c_void_p, c_void_p, _u32p, _u32p, _u32p, _u32p, _u64p, _u32p],
+    ),
+    "mirsha_streams_submit": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, _u32p,
+         _u64p],
+    ),
+    "mirsha_streams_submit_device": (
+        c_int,
+        [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, _u32p,
+         _u64p],
+    ),
     "mirsha_hash_batch_multi": (
         c_int,
         [c_void_p, c_int, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p],

@@ -10,28 +10,13 @@
 
 namespace mirsha {
 
-namespace {
-
-// The wave's issue priority, once at entry.  The priority is wave-uniform;
-// readfirstlane keeps the branches scalar, so exactly one s_setprio executes
-// (s_setprio ignores exec: fixed_prio, mirsha_kernels.hip).
-__device__ __forceinline__ void seg_prio(uint32_t p) {
-    p = (uint32_t)__builtin_amdgcn_readfirstlane((int)p);
-    if (p >= 3u) __builtin_amdgcn_s_setprio(3);
-    else if (p == 2u) __builtin_amdgcn_s_setprio(2);
-    else if (p == 1u) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(0);
-}
-
-}  // namespace
-
 // One lane per segment of the cycle's commit programme
 // (mirsha_commit_seg_plan): segment s runs entries ent[sfirst[s] ..
 // sfirst[s+1]) of chain seg_chain[s].  What differs from chains_commit_kernel:
 // a lane that is not its chain's FIRST segment loads no state (it starts from
 // Hasher()), one that is not the LAST stores none, the checkpoint rows are
 // plain 128-bit vector stores (`out` may be host-visible page-locked memory),
-// and the wave raises its issue priority once at entry: it is one
+// and the wave raises its issue priority once at entry (seg_prio): it is one
 // latency-bound wave meant to run beside a saturating request launch whose
 // waves run at priorities up to 3.  No atomics, no waiting; the only
 // cross-lane dependence is the ballot that keeps the loop wave-uniform.
@@ -124,15 +109,6 @@ hipError_t launch_chains_commit_seg(const uint8_t* digests, const uint32_t* ent,
 namespace mirsha_api {
 
 namespace {
-
-// The issue priority of the segment kernel's waves.  MIRSHA_AB=1
-// MIRSHA_COMMIT_PRIO=n (0-3) is the A/B knob.
-constexpr uint32_t kCommitSegPrio = 3;
-uint32_t commit_seg_prio() {
-    const char* e = mirsha::ab_getenv("MIRSHA_COMMIT_PRIO");
-    if (e && e[0] >= '0' && e[0] <= '3' && e[1] == 0) return (uint32_t)(e[0] - '0');
-    return kCommitSegPrio;
-}
 
 // Both forms of mirsha_chains_commit_submit.  Order: every check and the plan
 // (into the context's scratch; a failure leaves the ring as it was), then the

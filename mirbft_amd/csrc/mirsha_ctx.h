@@ -24,6 +24,8 @@
 //                       (mirsha_order.h; queue_bucket_order in mirsha_api.hip)
 //   mirsha_streams.hip  streaming hash states over any bytes (mirsha_streams_*)
 //                       and their kernel (mirsha_streams.h)
+//   mirsha_streams_ring.hip  a stream programme as a ticket of that ring
+//                       (mirsha_streams_submit*) and its segment kernel
 //   mirsha_host.cpp     host-only logic, no HIP (dedup scan, packing, the
 //                       expectation / commit / stream plans, a mixed ticket's kept-rows
 //                       walk): unit-tested on the CPU (tests/c)
@@ -172,13 +174,16 @@ struct ExpectSlot {
     DevBuf dev;         // stage's layout, then the verdict's (16-byte aligned)
 };
 
-// A commit submission (mirsha_chains_commit_submit*): the ring slot's own
-// copies of everything the device reads, so the caller's arrays are free when
-// the call returns.
+// A commit submission (mirsha_chains_commit_submit*) or a stream submission
+// (mirsha_streams_submit*): the ring slot's own copies of everything the device
+// reads, so the caller's arrays are free when the call returns.  A slot carries
+// one ticket at a time, so the two kinds share the buffers.
 struct CommitSlot {
-    PinnedBuf stage;  // [seg_chain | sfirst | seg_flags | ent | pad to 16 | host digest table]: ONE H2D
+    // commit: [seg_chain | sfirst | seg_flags | ent | pad to 16 | host digest table]
+    // stream: [seg_stream | sfirst | seg_flags | pad to 16 | entry records | packed bytes (host form)]
+    PinnedBuf stage;  // ONE H2D
     DevBuf dev;       // the same layout
-    DevBuf snap;      // [h | pend | cnt] as the launch found them (see commit_submit)
+    DevBuf snap;      // the states as the launch found them: [h | pend | cnt] (commit), the rows (stream)
     PinnedBuf rows;   // the values' rows when values_out is not kernel-writable
 };
 
@@ -190,7 +195,7 @@ enum class SlotRows : uint8_t {
     kCopyAll,  // rows [0, n) of the slot's `dig`
     kFanOut,   // row rank[i] of `dig` for request i (dedup)
     kKept,     // a mixed ticket's kept rows, from `dig` (mirsha::host::copy_kept_rows)
-    kCommit,   // n checkpoint values from cm.rows
+    kCommit,   // n values from cm.rows: a commit ticket's checkpoints, a stream ticket's sums
 };
 enum class SlotVerdict : uint8_t {
     kNone,
@@ -201,7 +206,7 @@ struct SlotRetire {
     SlotRows rows = SlotRows::kInPlace;
     SlotVerdict verdict = SlotVerdict::kNone;
     uint8_t* out = nullptr;  // digests_out / values_out
-    uint32_t n = 0;          // its rows: requests, or checkpoint values
+    uint32_t n = 0;          // its rows: requests, or checkpoint / sum values
     uint64_t* bits = nullptr;  // bits_out (may be NULL) and n_mismatch_out of a ticket that owes a verdict
     uint32_t* count = nullptr;
 };
@@ -281,7 +286,7 @@ struct mirsha_ctx {
     AsyncSlot slots[kAsyncSlots];
     std::vector<uint64_t> xp_has;   // mirsha_expect_plan of the submission being validated
     std::vector<uint32_t> xp_base;
-    hipStream_t xcommit = nullptr;  // commit submissions (created at the first one)
+    hipStream_t xcommit = nullptr;  // commit and stream submissions (created at the first one)
     std::vector<uint32_t> cm_plan;  // mirsha_commit_seg_plan of the submission being validated
     uint64_t next_ticket = 1;  // ticket of the next submission
     uint64_t done_ticket = 0;  // every ticket <= this one has completed
@@ -302,6 +307,27 @@ struct mirsha_chains {
     // the synchronous calls make their stream wait for it, destroy waits for it.
     hipEvent_t ev_commit = nullptr;
     bool commit_queued = false;
+};
+
+// Streaming hash states (see mirsha.h, mirsha_streams_create).
+struct mirsha_streams {
+    int device = 0;
+    uint32_t n = 0;
+    DevBuf d_state;  // kStreamStateBytes per stream (mirsha_streams.h)
+    // mirsha_stream_plan's arrays of the call being run or submitted, and
+    // mirsha_stream_seg_plan's of a submission (kept across calls)
+    std::vector<uint32_t> act, efirst, kind, len;
+    std::vector<uint64_t> off, poff;
+    std::vector<uint32_t> seg_stream, sfirst, seg_flags;
+    // mirsha_streams_run's block [act | efirst | pad to 16 | entries {kind, len,
+    // off lo, off hi} | the written bytes, each distinct range once (host
+    // form)]: ONE H2D copy.
+    PinnedBuf stage;
+    DevBuf dev, d_out;
+    // The last stream submission queued on this object (mirsha_streams_submit*):
+    // the synchronous calls make their stream wait for it, destroy waits for it.
+    hipEvent_t ev_run = nullptr;
+    bool run_queued = false;
 };
 
 // A request -> batch-digest pipeline plan (see mirsha.h, mirsha_pipeline_create).
@@ -409,6 +435,24 @@ inline int chains_order(mirsha_ctx* c, mirsha_chains* ch) {
     if (!ch->commit_queued) return MIRSHA_OK;
     HIP_TRY(c, hipStreamWaitEvent(c->stream, ch->ev_commit, 0));
     return MIRSHA_OK;
+}
+
+// The same for the streams' last queued stream submission.
+inline int streams_order(mirsha_ctx* c, mirsha_streams* st) {
+    if (!st->run_queued) return MIRSHA_OK;
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, st->ev_run, 0));
+    return MIRSHA_OK;
+}
+
+// The issue priority of the segment kernels' waves (seg_prio, mirsha_device.h).
+// MIRSHA_AB=1 MIRSHA_COMMIT_PRIO=n (0-3) is the A/B knob of both.  3 was
+// measured for the commit wave only; the stream wave takes
+// it unmeasured.
+constexpr uint32_t kCommitSegPrio = 3;
+inline uint32_t commit_seg_prio() {
+    const char* e = mirsha::ab_getenv("MIRSHA_COMMIT_PRIO");
+    if (e && e[0] >= '0' && e[0] <= '3' && e[1] == 0) return (uint32_t)(e[0] - '0');
+    return kCommitSegPrio;
 }
 
 int check_lists(mirsha_ctx* c, const uint32_t* idx, const uint32_t* first, uint32_t n_lists, uint32_t n_digests);

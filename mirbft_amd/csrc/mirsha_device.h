@@ -1,6 +1,7 @@
 // mirsha_device.h — what the .hip units share beyond the compression itself
-// (sha256_device.h): the one launch path, the digest-list primitives of the
-// dependent-pass kernels and the step of a commit programme.  HIP only:
+// (sha256_device.h): the one launch path, the issue priority of the segment
+// kernels, the digest-list primitives of the dependent-pass kernels and the
+// step of a commit programme.  HIP only:
 // mirsha_host.cpp (plain C++) never includes it.
 #pragma once
 #include <hip/hip_ext.h>
@@ -25,6 +26,20 @@ void launch_k(void (*k)(P...), dim3 grid, dim3 block, uint32_t shmem, hipStream_
     } else {
         k<<<grid, block, shmem, s>>>(static_cast<P>(args)...);
     }
+}
+
+// ---- issue priority -------------------------------------------------------
+// The wave's issue priority, once at entry of the two segment kernels
+// (chains_commit_seg_kernel, mirsha_commit_ring.hip; streams_seg_kernel,
+// mirsha_streams_ring.hip).  The priority is wave-uniform; readfirstlane keeps
+// the branches scalar, so exactly one s_setprio executes (s_setprio ignores
+// exec: fixed_prio, mirsha_kernels.hip).
+__device__ __forceinline__ void seg_prio(uint32_t p) {
+    p = (uint32_t)__builtin_amdgcn_readfirstlane((int)p);
+    if (p >= 3u) __builtin_amdgcn_s_setprio(3);
+    else if (p == 2u) __builtin_amdgcn_s_setprio(2);
+    else if (p == 1u) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
 }
 
 // ---- digest lists ---------------------------------------------------------

@@ -1069,3 +1069,57 @@ extern "C" int mirsha_stream_plan(const uint32_t* op_stream, const uint32_t* op_
     *n_bytes_out = bytes;
     return MIRSHA_OK;
 }
+
+// mirsha_stream_plan's per-stream programmes cut after every SUM_RESET and
+// RESET entry, as mirsha_commit_seg_plan cuts a chain's after every
+// checkpoint: behind either the stream restarts from Hasher(), so the
+// stretches are independent hashes (one lane each, mirsha_streams_submit).
+// The entries stay where mirsha_stream_plan put them; sfirst indexes them.
+extern "C" int mirsha_stream_seg_plan(const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
+                                      const uint32_t* op_len, uint32_t n_ops, uint32_t n_streams, uint64_t arena_len,
+                                      int pack, uint32_t* seg_stream_out, uint32_t* sfirst_out,
+                                      uint32_t* seg_flags_out, uint32_t* ent_kind_out, uint64_t* ent_off_out,
+                                      uint32_t* ent_len_out, uint32_t* n_seg_out, uint32_t* n_active_out,
+                                      uint32_t* n_entries_out, uint32_t* n_values_out, uint64_t* n_bytes_out,
+                                      uint32_t* bad_op_out) {
+    if (bad_op_out) *bad_op_out = UINT32_MAX;
+    if (!n_seg_out || !n_active_out || !n_entries_out || !n_values_out || !n_bytes_out) return MIRSHA_EINVAL;
+    *n_seg_out = 0;
+    if (n_ops && (!seg_stream_out || !sfirst_out || !seg_flags_out || !ent_kind_out || !ent_off_out || !ent_len_out)) {
+        // the argument checks of mirsha_stream_plan come first (its codes, its bad op)
+        const int rc = mirsha_stream_plan(op_stream, op_kind, op_off, op_len, n_ops, n_streams, arena_len, pack,
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, n_active_out, n_entries_out,
+                                          n_values_out, n_bytes_out, bad_op_out);
+        return rc != MIRSHA_OK ? rc : MIRSHA_EINVAL;
+    }
+    const uint32_t cap = std::min(n_ops, n_streams);
+    std::vector<uint32_t> act, efirst;
+    try {
+        act.assign((size_t)cap, 0);
+        efirst.assign((size_t)cap + 1, 0);
+    } catch (const std::bad_alloc&) {
+        return MIRSHA_ENOMEM;
+    }
+    const int rc = mirsha_stream_plan(op_stream, op_kind, op_off, op_len, n_ops, n_streams, arena_len, pack, act.data(),
+                                      efirst.data(), ent_kind_out, ent_off_out, ent_len_out, n_active_out,
+                                      n_entries_out, n_values_out, n_bytes_out, bad_op_out);
+    if (rc != MIRSHA_OK) return rc;
+    if (sfirst_out) sfirst_out[0] = 0;
+    uint32_t ns = 0;
+    for (uint32_t k = 0; k < *n_active_out; k++) {
+        const uint32_t e0 = efirst[k], e1 = efirst[k + 1];  // e1 > e0: the stream is active
+        uint32_t start = e0;
+        for (uint32_t e = e0; e < e1; e++) {
+            // a segment ends with an entry that leaves Hasher(), or with the stream's final entry
+            const uint32_t kind = ent_kind_out[e] & 3u;
+            if (kind != MIRSHA_STREAM_SUM_RESET && kind != MIRSHA_STREAM_RESET && e + 1 < e1) continue;
+            seg_stream_out[ns] = act[k];
+            seg_flags_out[ns] =
+                (start == e0 ? MIRSHA_STREAM_SEG_FIRST : 0u) | (e + 1 == e1 ? MIRSHA_STREAM_SEG_LAST : 0u);
+            sfirst_out[++ns] = e + 1;
+            start = e + 1;
+        }
+    }
+    *n_seg_out = ns;
+    return MIRSHA_OK;
+}

@@ -131,10 +131,10 @@ void copy_kept_rows(const uint64_t* has, const uint64_t* mis, uint32_t n, const 
 uint32_t order_chunk(uint32_t bins);
 
 // The packed layout of a stream programme's written bytes (mirsha_stream_plan
-// with pack, mirsha_streams_run): poff_out[e] = where entry e's bytes lie
-// (0 for an entry without bytes); returns the packed size.  A first entry of
-// a range is the one whose offset equals the bytes packed before it.
-// poff_out may be `off` itself.
+// and mirsha_stream_seg_plan with pack, mirsha_streams_run / _submit):
+// poff_out[e] = where entry e's bytes lie (0 for an entry without bytes);
+// returns the packed size.  A first entry of a range is the one whose offset
+// equals the bytes packed before it.  poff_out may be `off` itself.
 uint64_t stream_pack_offsets(const uint64_t* off, const uint32_t* len, uint32_t entries, uint64_t* poff_out);
 
 // Copies request which[k] (k < m) to dst + dst_off[k], in parallel.  With

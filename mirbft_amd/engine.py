@@ -144,6 +144,18 @@ class CommitTicket(Ticket):
         return self.out
 
 
+class StreamTicket(Ticket):
+    """A submission of HashStreams.submit / submit_device / submit_flush.
+    ``values`` (= ``out``), shape (k, 32): one row per STREAM_SUM /
+    STREAM_SUM_RESET op, in op order; complete after ``Engine.wait`` (or a
+    ``poll`` that reports done).  A ``submit_flush`` ticket's rows are in the
+    order of its hashers."""
+
+    @property
+    def values(self) -> np.ndarray:
+        return self.out
+
+
 def _out_rows(out, n: int) -> np.ndarray:
     """A caller-supplied (n, 32) uint8 result array (checked), or a new one."""
     if out is None:
@@ -976,6 +988,39 @@ def stream_plan(ops, n_streams: int, arena_len: int, pack: bool = False):
             nb.value)
 
 
+def stream_seg_plan(ops, n_streams: int, arena_len: int, pack: bool = False):
+    """Host-only mirsha_stream_seg_plan: ``stream_plan``'s per-stream programmes
+    cut after every STREAM_SUM_RESET and STREAM_RESET entry, one segment per
+    lane of the ring form (``HashStreams.submit``).  Returns (seg_stream,
+    sfirst, seg_flags, ent_kind, ent_off, ent_len, n_values, n_bytes, n_active):
+    segment s belongs to stream ``seg_stream[s]`` and runs entries
+    ``sfirst[s]:sfirst[s+1]`` of the entry arrays (stream_plan's, unchanged);
+    ``seg_flags[s]`` has MIRSHA_STREAM_SEG_FIRST on the stream's first segment
+    (it starts from the stored state, every other one from Hasher()) and
+    MIRSHA_STREAM_SEG_LAST on the one holding the stream's final entry."""
+    os_, ok, oo, ol = _stream_ops(ops)
+    seg_stream = np.zeros(os_.size, dtype=np.uint32)
+    sfirst = np.zeros(os_.size + 1, dtype=np.uint32)
+    seg_flags = np.zeros(os_.size, dtype=np.uint32)
+    kind = np.zeros(os_.size, dtype=np.uint32)
+    off = np.zeros(os_.size, dtype=np.uint64)
+    ln = np.zeros(os_.size, dtype=np.uint32)
+    ns, na, ne, nv, bad = (ctypes.c_uint32(0) for _ in range(5))
+    nb = ctypes.c_uint64(0)
+    rc = _lib.load().mirsha_stream_seg_plan(_ptr(os_), _ptr(ok), _ptr(oo), _ptr(ol), os_.size, int(n_streams),
+                                            int(arena_len), 1 if pack else 0, _ptr(seg_stream), sfirst.ctypes.data,
+                                            _ptr(seg_flags), _ptr(kind), _ptr(off), _ptr(ln), ctypes.byref(ns),
+                                            ctypes.byref(na), ctypes.byref(ne), ctypes.byref(nv), ctypes.byref(nb),
+                                            ctypes.byref(bad))
+    if rc != _lib.MIRSHA_OK:
+        err = MirshaError(rc, f"stream segment plan: op {bad.value}" if bad.value != 0xFFFFFFFF
+                          else "stream segment plan: arguments")
+        err.bad_op = None if bad.value == 0xFFFFFFFF else bad.value
+        raise err
+    return (seg_stream[:ns.value], sfirst[:ns.value + 1], seg_flags[:ns.value], kind[:ne.value], off[:ne.value],
+            ln[:ne.value], nv.value, nb.value, na.value)
+
+
 class HashStreams:
     """Streaming SHA-256 states on the device (mirsha_streams_*): n hashers in
     the reference's own shape, ``type Hasher func() hash.Hash``
@@ -983,8 +1028,11 @@ class HashStreams:
     without disturbing the state, Reset -- whose midstate, unfinished block and
     length stay on the device across calls.  ``run`` is ONE programme over any
     number of streams in ONE launch; ``hasher()`` / ``flush`` is the hash.Hash
-    form on top of it.  ``bytes_sent`` counts the bytes of the distinct ranges
-    the write ops of each ``run`` named (what crossed PCIe); ``runs`` the calls."""
+    form on top of it.  ``submit`` / ``submit_device`` / ``submit_flush`` are
+    the same as tickets of the engine's ring (one lane per stretch between
+    resets, beside the hashing).  ``bytes_sent`` counts the bytes of the
+    distinct ranges the write ops of each ``run`` / ``submit`` named (what
+    crossed PCIe); ``runs`` the calls."""
 
     def __init__(self, engine: Engine, n_streams: int):
         self._engine = engine
@@ -1019,12 +1067,55 @@ class HashStreams:
                                  _ptr(ol), os_.size, _ptr(out), ctypes.byref(k)))
         if k.value != out.shape[0]:
             raise MirshaError(_lib.MIRSHA_EHIP, f"streams: {k.value} values for {out.shape[0]} sums")
-        if call is self._lib.mirsha_streams_run:
-            w = (ok == _lib.MIRSHA_STREAM_WRITE) & (ol != 0)
-            ranges = np.unique(np.stack([oo[w], ol[w].astype(np.uint64)]), axis=1)
-            self.bytes_sent += int(ranges[1].sum())
-        self.runs += 1
+        self._count(call is self._lib.mirsha_streams_run, ok, oo, ol)
         return out
+
+    def _count(self, host: bool, ok, oo, ol) -> None:
+        if host:  # every distinct (off, len) range once: a sort and a compare with the neighbour
+            w = (ok == _lib.MIRSHA_STREAM_WRITE) & (ol != 0)
+            off, ln = oo[w], ol[w]
+            order = np.lexsort((ln, off))
+            off, ln = off[order], ln[order]
+            again = (off[1:] == off[:-1]) & (ln[1:] == ln[:-1])
+            self.bytes_sent += int(ln.sum(dtype=np.uint64)) - int(ln[1:][again].sum(dtype=np.uint64))
+        self.runs += 1
+
+    def submit(self, ops, arena=b"", out=None) -> "StreamTicket":
+        """run() as a submission of the engine's ring (mirsha_streams_submit):
+        the programme is checked, planned and copied (ops and written bytes)
+        before this returns, the device runs it on the engine's commit stream
+        beside whatever hashing is queued, one lane per stretch between
+        Sum-then-Reset / Reset ops, and ``engine.wait(ticket)`` returns the
+        digests, (k, 32) uint8 in op order.  Tickets retire in submission
+        order, mixed with the hashing and commit tickets.  A page-locked
+        ``out`` (``engine.host_empty``) receives the values from the kernel
+        itself."""
+        a = _as_u8(arena)
+        return self._submit(self._lib.mirsha_streams_submit, _ptr(a), a.size, ops, out, None)
+
+    def submit_device(self, ops, d_arena: int, arena_len: int, out=None, keep=None) -> "StreamTicket":
+        """submit() with the arena in device memory (a raw device address, any
+        alignment): it is read behind whatever is queued on the engine's
+        stream at this moment, e.g. the ``hash_batch_device`` that writes it,
+        and must stay intact until the ticket retires (``keep``: an object to
+        hold on to until then)."""
+        return self._submit(self._lib.mirsha_streams_submit_device, int(d_arena) or None, int(arena_len), ops, out,
+                            keep)
+
+    def _submit(self, call, arena, arena_len: int, ops, out, keep) -> "StreamTicket":
+        os_, ok, oo, ol = _stream_ops(ops)
+        sums = (ok == _lib.MIRSHA_STREAM_SUM) | (ok == _lib.MIRSHA_STREAM_SUM_RESET)
+        out = _out_rows(out, int(np.count_nonzero(sums)))
+        k, t = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        eng = self._engine
+        eng._check(call(eng.ctx, self.handle, arena, arena_len, _ptr(os_), _ptr(ok), _ptr(oo), _ptr(ol), os_.size,
+                        _ptr(out), ctypes.byref(k), ctypes.byref(t)))
+        if k.value != out.shape[0]:
+            raise MirshaError(_lib.MIRSHA_EHIP, f"streams: {k.value} values for {out.shape[0]} sums")
+        self._count(call is self._lib.mirsha_streams_submit, ok, oo, ol)
+        eng._outstanding[t.value] = (out, keep, self)  # the streams too: the kernel writes their state
+        eng._retire(t.value - ASYNC_SLOTS)
+        return StreamTicket(t.value, out)
 
     def export_state(self, which) -> np.ndarray:
         """The states of streams ``which`` as (k, 108) uint8 rows in the layout
@@ -1062,6 +1153,25 @@ class HashStreams:
         """Sends the pending Resets and writes of ``hashers`` -- and with
         ``sums`` one Sum each -- in ONE ``run``: the batched use.  Returns the
         digests (bytes) in the order of ``hashers``, or [] without sums."""
+        ops, arena = self._flush_programme(hashers, sums)
+        out = self.run(ops, arena) if ops else np.empty((0, 32), dtype=np.uint8)
+        for hs in hashers:  # sent: only now, a refused run leaves them pending
+            hs._pending, hs._reset = [], False
+        return [row.tobytes() for row in out]
+
+    def submit_flush(self, hashers, sums: bool = True) -> "StreamTicket":
+        """flush() as ONE ``submit``: the hashers are marked sent when this
+        returns (a refused submission leaves them pending), and
+        ``engine.wait(ticket)`` gives the digests, one row per hasher in the
+        order of ``hashers`` ((0, 32) without sums)."""
+        ops, arena = self._flush_programme(hashers, sums)
+        ticket = self.submit(ops, arena)
+        for hs in hashers:
+            hs._pending, hs._reset = [], False
+        return ticket
+
+    def _flush_programme(self, hashers, sums: bool):
+        """(ops, arena) of the pending Resets and writes of ``hashers``."""
         ops, parts, at = [], [], 0
         for hs in hashers:
             if hs._streams is not self or hs.stream is None:
@@ -1075,10 +1185,7 @@ class HashStreams:
                 at += size
             if sums:
                 ops.append((hs.stream, _lib.MIRSHA_STREAM_SUM, 0, 0))
-        out = self.run(ops, b"".join(parts)) if ops else np.empty((0, 32), dtype=np.uint8)
-        for hs in hashers:  # sent: only now, a refused run leaves them pending
-            hs._pending, hs._reset = [], False
-        return [row.tobytes() for row in out]
+        return ops, b"".join(parts)
 
     def close(self) -> None:
         if getattr(self, "handle", None):

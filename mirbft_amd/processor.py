@@ -20,7 +20,8 @@ one kernel launch over the device-resident checkpoint chains
 raise; a cycle without commits touches no log.
 ``async_commits=True``: ``submit()`` (and so ``ProcessorWorkPool.process``)
 queues the cycle's commits as a ticket of the engine's ring
-(``DeviceLog.submit_cycle`` -> ``CheckpointChains.submit_commit``) ahead of the
+(``DeviceLog.submit_cycle`` -> ``CheckpointChains.submit_commit``, or
+``StreamLog.submit_cycle`` -> ``HashStreams.submit``) ahead of the
 hashing instead of applying them first, and ``PendingResults.wait()`` collects
 them: commitInParallel beside hashInParallel (processor.go:447-470).
 
@@ -235,6 +236,9 @@ class StreamLog:
     ``values`` is (checkpoints, n_nodes, 32) as ``DeviceLog``'s.  Every node's
     write op names the same range of the cycle's arena, and ``run`` sends each
     distinct range once: a cycle's bytes cross PCIe once, whatever n_nodes is.
+    ``submit_cycle`` / ``collect_cycle`` are the asynchronous form
+    (``HashStreams.submit``), with the contract of ``DeviceLog``'s: cycles take
+    effect in submission order, whatever the order they are collected in.
     ``DeviceLog`` stays the log for digest-only applications."""
 
     def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, entry_data=None, streams=None):
@@ -267,6 +271,18 @@ class StreamLog:
     def commit_cycle(self, commits) -> list:
         ops, arena = self.cycle_programme(commits)
         self.values = self.streams.run(ops, arena).reshape(-1, self.n_nodes, 32)
+        return [v.tobytes() for v in self.values[:, self.node]]
+
+    def submit_cycle(self, commits):
+        """Queues one cycle's commits (``HashStreams.submit``, a ticket of the
+        engine's ring); returns the ticket ``collect_cycle`` takes."""
+        ops, arena = self.cycle_programme(commits)
+        return self.streams.submit(ops, arena)
+
+    def collect_cycle(self, ticket) -> list:
+        """Waits for a cycle queued by ``submit_cycle``: node ``node``'s value
+        per checkpoint, in commit order; ``values`` holds every node's."""
+        self.values = self._engine.wait(ticket).reshape(-1, self.n_nodes, 32)
         return [v.tobytes() for v in self.values[:, self.node]]
 
     def close(self) -> None:
