@@ -128,6 +128,23 @@ int queue_bucket_order(mirsha_ctx* c, const OrderShape& sh, const uint32_t* d_le
     });
 }
 
+int commit_args(mirsha_ctx* c, const mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
+                const uint32_t* op_chain, const uint32_t* op_digest) {
+    if (!op_chain || !op_digest) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (n_digests && !digests) return fail(c, MIRSHA_EINVAL, "NULL digest table (%u digests)", n_digests);
+    if (on_device && (reinterpret_cast<uintptr_t>(digests) & 15u))
+        return fail(c, MIRSHA_EINVAL, "d_digests must be 16-byte aligned");
+    if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
+    return MIRSHA_OK;
+}
+
+int commit_plan_failed(mirsha_ctx* c, int rc, uint32_t bad, const mirsha_chains* ch, uint32_t n_digests,
+                       const uint32_t* op_chain, const uint32_t* op_digest) {
+    if (bad == UINT32_MAX) return fail(c, rc, "commit plan failed");
+    if (op_chain[bad] >= ch->n) return fail(c, rc, "op_chain[%u] = %u >= %u", bad, op_chain[bad], ch->n);
+    return fail(c, rc, "op_digest[%u] = %u >= %u", bad, op_digest[bad], n_digests);
+}
+
 }  // namespace mirsha_api
 
 extern "C" {
@@ -428,10 +445,7 @@ int mirsha_chains_create(mirsha_ctx* c, uint32_t n, mirsha_chains** out) {
 void mirsha_chains_destroy(mirsha_chains* ch) {
     if (!ch) return;
     (void)hipSetDevice(ch->device);
-    if (ch->ev_commit) {  // the last queued commit submission still uses the state
-        (void)hipEventSynchronize(ch->ev_commit);
-        (void)hipEventDestroy(ch->ev_commit);
-    }
+    owner_retire(ch->ring);
     for (DevBuf* b : {&ch->d_h, &ch->d_pend, &ch->d_cnt, &ch->d_dig, &ch->d_pos, &ch->d_act, &ch->d_afirst,
                       &ch->d_which, &ch->d_out, &ch->d_plan})
         b->release();
@@ -460,7 +474,7 @@ int mirsha_chains_absorb(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
     std::vector<uint32_t> pos(m);
     for (uint32_t i = 0; i < m; i++) pos[count[chain_of[i]]++] = i;
     if (int rc = use_device(c)) return rc;
-    if (int rc = chains_order(c, ch)) return rc;
+    if (int rc = owner_order(c, ch->ring)) return rc;
     const uint32_t na = (uint32_t)act.size();
     HIP_TRY(c, ch->d_dig.ensure(32ull * m));
     HIP_TRY(c, ch->d_pos.ensure(4ull * m));
@@ -488,7 +502,7 @@ int chains_which(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32
     for (uint32_t j = 0; j < k; j++)
         if (which[j] >= ch->n) return fail(c, MIRSHA_EINVAL, "which[%u] = %u >= %u", j, which[j], ch->n);
     if (int rc = use_device(c)) return rc;
-    if (int rc = chains_order(c, ch)) return rc;
+    if (int rc = owner_order(c, ch->ring)) return rc;
     HIP_TRY(c, ch->d_which.ensure(4ull * k));
     HIP_TRY(c, hipMemcpyAsync(ch->d_which.p, which, 4ull * k, hipMemcpyHostToDevice, c->stream));
     return MIRSHA_OK;
@@ -537,11 +551,7 @@ static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
     if (!c || !ch || !n_values_out) return MIRSHA_EINVAL;
     *n_values_out = 0;
     if (n_ops == 0) return MIRSHA_OK;
-    if (!op_chain || !op_digest) return fail(c, MIRSHA_EINVAL, "NULL argument");
-    if (n_digests && !digests) return fail(c, MIRSHA_EINVAL, "NULL digest table (%u digests)", n_digests);
-    if (on_device && (reinterpret_cast<uintptr_t>(digests) & 15u))
-        return fail(c, MIRSHA_EINVAL, "d_digests must be 16-byte aligned");
-    if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
+    if (int r = commit_args(c, ch, digests, on_device, n_digests, op_chain, op_digest)) return r;
     const uint32_t cap = std::min(n_ops, ch->n);  // active chains at most
     const size_t o_first = cap, o_ent = 2ull * cap + 1u;
     ch->plan.resize(o_ent + n_ops);
@@ -551,15 +561,11 @@ static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
                                       &na, &entries, &values, &bad);
     if (rc == MIRSHA_ERANGE)
         return fail(c, rc, "%u ops / %u digests > %u", n_ops, n_digests, MIRSHA_COMMIT_ENTRY_CHECKPOINT);
-    if (rc != MIRSHA_OK) {
-        if (bad == UINT32_MAX) return fail(c, rc, "commit plan failed");
-        if (op_chain[bad] >= ch->n) return fail(c, rc, "op_chain[%u] = %u >= %u", bad, op_chain[bad], ch->n);
-        return fail(c, rc, "op_digest[%u] = %u >= %u", bad, op_digest[bad], n_digests);
-    }
+    if (rc != MIRSHA_OK) return commit_plan_failed(c, rc, bad, ch, n_digests, op_chain, op_digest);
     if (values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u checkpoints)", values);
     if (na == 0) return MIRSHA_OK;  // null writes only
     if (int r = use_device(c)) return r;
-    if (int r = chains_order(c, ch)) return r;
+    if (int r = owner_order(c, ch->ring)) return r;
     const uint8_t* d_dig = digests;
     if (!on_device && n_digests) {
         HIP_TRY(c, ch->d_dig.ensure(32ull * n_digests));

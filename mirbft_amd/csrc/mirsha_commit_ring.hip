@@ -110,138 +110,61 @@ namespace mirsha_api {
 
 namespace {
 
-// Both forms of mirsha_chains_commit_submit.  Order: every check and the plan
-// (into the context's scratch; a failure leaves the ring as it was), then the
-// ring's slot lifecycle (mirsha_ctx.h): the slot, the staging copy, the device
-// work on the commit stream, the ticket.
+// Both forms of mirsha_chains_commit_submit: every check and the plan (into
+// the context's scratch; a failure leaves the ring as it was), then the segment
+// ticket's slot lifecycle (seg_submit, mirsha_ctx.h).
 int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
                   const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
                   uint32_t* n_values_out, uint64_t* ticket_out) {
     if (!c || !ch || !n_values_out || !ticket_out) return MIRSHA_EINVAL;
     *n_values_out = 0;
-    auto t0 = Clock::now();
-    double ph[MIRSHA_PROF_PHASES] = {};
-    uint32_t ns = 0, na = 0, entries = 0, values = 0;
+    const auto t0 = Clock::now();
+    SegTicket t;
+    uint32_t na = 0, entries = 0;
     const size_t o_pfirst = n_ops, o_pflags = 2ull * n_ops + 1u, o_pent = 3ull * n_ops + 1u;  // in c->cm_plan
     if (n_ops) {
-        if (!op_chain || !op_digest) return fail(c, MIRSHA_EINVAL, "NULL argument");
-        if (n_digests && !digests) return fail(c, MIRSHA_EINVAL, "NULL digest table (%u digests)", n_digests);
-        if (on_device && (reinterpret_cast<uintptr_t>(digests) & 15u))
-            return fail(c, MIRSHA_EINVAL, "d_digests must be 16-byte aligned");
-        if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
+        if (int rc = commit_args(c, ch, digests, on_device, n_digests, op_chain, op_digest)) return rc;
         if (n_ops > MIRSHA_COMMIT_ENTRY_CHECKPOINT || n_digests > MIRSHA_COMMIT_ENTRY_CHECKPOINT)
             return fail(c, MIRSHA_ERANGE, "%u ops / %u digests > %u", n_ops, n_digests, MIRSHA_COMMIT_ENTRY_CHECKPOINT);
         if (c->cm_plan.size() < o_pent + n_ops) c->cm_plan.resize(o_pent + n_ops);
         uint32_t* plan = c->cm_plan.data();
         uint32_t bad = UINT32_MAX;
         const int rc = mirsha_commit_seg_plan(op_chain, op_digest, n_ops, ch->n, n_digests, plan, plan + o_pfirst,
-                                              plan + o_pflags, plan + o_pent, &ns, &na, &entries, &values, &bad);
-        if (rc != MIRSHA_OK) {
-            if (bad == UINT32_MAX) return fail(c, rc, "commit plan failed");
-            if (op_chain[bad] >= ch->n) return fail(c, rc, "op_chain[%u] = %u >= %u", bad, op_chain[bad], ch->n);
-            return fail(c, rc, "op_digest[%u] = %u >= %u", bad, op_digest[bad], n_digests);
-        }
-        if (values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u checkpoints)", values);
+                                              plan + o_pflags, plan + o_pent, &t.n_seg, &na, &entries, &t.values, &bad);
+        if (rc != MIRSHA_OK) return commit_plan_failed(c, rc, bad, ch, n_digests, op_chain, op_digest);
+        if (t.values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u checkpoints)", t.values);
+        t.seg_flags = plan + o_pflags;
     }
-    ph[MIRSHA_PROF_VALIDATE] = ms_since(t0);
-    t0 = Clock::now();
-    AsyncSlot* slot = nullptr;
-    if (int rc = ring_acquire(c, &slot)) return rc;
-    AsyncSlot& sl = *slot;
-    CommitSlot& cm = sl.cm;
-    if (ns) {
-        if (!c->xcommit) HIP_TRY(c, hipStreamCreateWithFlags(&c->xcommit, hipStreamNonBlocking));
-        if (int rc = ensure_event(c, &ch->ev_commit)) return rc;
-        if (on_device)
-            if (int rc = ensure_event(c, &sl.ev_in)) return rc;
-    }
-    RingQueued queued(c->xcommit);
     // The slot's block: [seg_chain | sfirst | seg_flags | ent | pad to 16 | host table].
-    const uint64_t o_first = 4ull * ns, o_flags = o_first + 4ull * (ns + 1u), o_ent = o_flags + 4ull * ns;
+    const uint64_t ns = t.n_seg, o_first = 4ull * ns, o_flags = o_first + 4ull * (ns + 1u), o_ent = o_flags + 4ull * ns;
     const uint64_t o_tab = align16(o_ent + 4ull * entries);
-    const uint64_t bytes = o_tab + (on_device ? 0ull : 32ull * n_digests);
-    // Does a chain's FIRST segment lie in another wave than its LAST?  Then the
-    // FIRST lanes read a copy of the states taken ahead of the launch.
-    bool straddle = false;
-    uint8_t* rows = nullptr;
-    if (ns) {
-        const uint32_t* plan = c->cm_plan.data();
-        uint32_t first_wave = 0;
-        for (uint32_t s = 0; s < ns && !straddle; s++) {
-            if (plan[o_pflags + s] & MIRSHA_COMMIT_SEG_FIRST) first_wave = s >> 6;
-            if ((plan[o_pflags + s] & MIRSHA_COMMIT_SEG_LAST) && (s >> 6) != first_wave) straddle = true;
-        }
-        HIP_TRY(c, cm.stage.ensure(bytes));
-        HIP_TRY(c, cm.dev.ensure(bytes));
-        if (straddle) HIP_TRY(c, cm.snap.ensure(72ull * ch->n));
-        if (values) {
-            // a kernel-writable values_out receives the values from the kernel
-            // itself, else the slot's rows do, copied out at retirement
-            rows = host_rows(c, values_out);
-            if (!rows) {
-                HIP_TRY(c, cm.rows.ensure(32ull * values));
-                if (int rc = pinned_rows(c, cm.rows, &rows)) return rc;
-                sl.retire.rows = SlotRows::kCommit;
-                sl.retire.out = values_out;
-                sl.retire.n = values;
-            }
-        }
-    }
-    ph[MIRSHA_PROF_PLAN] = ms_since(t0);
-    t0 = Clock::now();
-    auto queue = [&]() -> int {
-        const uint32_t* plan = c->cm_plan.data();
-        uint8_t* st = cm.stage.as<uint8_t>();
-        memcpy(st, plan, 4ull * ns);
-        memcpy(st + o_first, plan + o_pfirst, 4ull * (ns + 1u));
-        memcpy(st + o_flags, plan + o_pflags, 4ull * ns);
-        memcpy(st + o_ent, plan + o_pent, 4ull * entries);
-        if (!on_device && n_digests) memcpy(st + o_tab, digests, 32ull * n_digests);
-        hipStream_t q = c->xcommit;
-        queued.arm();
-        if (on_device) {  // the table is read behind whatever was queued on the context's stream
-            HIP_TRY(c, hipEventRecord(sl.ev_in, c->stream));
-            HIP_TRY(c, hipStreamWaitEvent(q, sl.ev_in, 0));
-        }
-        HIP_TRY(c, hipMemcpyAsync(cm.dev.p, st, bytes, hipMemcpyHostToDevice, q));
-        uint32_t* h = ch->d_h.as<uint32_t>();
-        uint32_t* pend = ch->d_pend.as<uint32_t>();
-        uint64_t* cnt = ch->d_cnt.as<uint64_t>();
-        const uint32_t *h_in = h, *pend_in = pend;
-        const uint64_t* cnt_in = cnt;
-        if (straddle) {
-            uint8_t* sn = cm.snap.as<uint8_t>();
-            const uint64_t nc = ch->n;
-            HIP_TRY(c, hipMemcpyAsync(sn, h, 32ull * nc, hipMemcpyDeviceToDevice, q));
-            HIP_TRY(c, hipMemcpyAsync(sn + 32ull * nc, pend, 32ull * nc, hipMemcpyDeviceToDevice, q));
-            HIP_TRY(c, hipMemcpyAsync(sn + 64ull * nc, cnt, 8ull * nc, hipMemcpyDeviceToDevice, q));
-            h_in = reinterpret_cast<const uint32_t*>(sn);
-            pend_in = reinterpret_cast<const uint32_t*>(sn + 32ull * nc);
-            cnt_in = reinterpret_cast<const uint64_t*>(sn + 64ull * nc);
-        }
-        const uint8_t* dv = cm.dev.as<uint8_t>();
-        const uint8_t* d_dig = on_device ? digests : dv + o_tab;
-        const uint32_t prio = commit_seg_prio();
-        if (int rc = timed_launch(c, 1, [&] {
-                return mirsha::launch_chains_commit_seg(
-                    d_dig, reinterpret_cast<const uint32_t*>(dv + o_ent), reinterpret_cast<const uint32_t*>(dv),
-                    reinterpret_cast<const uint32_t*>(dv + o_first), reinterpret_cast<const uint32_t*>(dv + o_flags),
-                    ns, h_in, pend_in, cnt_in, h, pend, cnt, rows, prio, q);
-            }))
-            return rc;
-        HIP_TRY(c, hipEventRecord(sl.done, q));
-        HIP_TRY(c, hipEventRecord(ch->ev_commit, q));
-        return MIRSHA_OK;
-    };
-    if (ns) {
-        if (int rc = queue()) return rc;  // (what it queued is drained: RingQueued)
-        ch->commit_queued = true;
-    }
-    sl.t_queued = Clock::now();
-    ph[MIRSHA_PROF_PACK] = ms_since(t0);
-    *n_values_out = values;
-    ring_publish(c, sl, queued, ph, ticket_out);
-    return MIRSHA_OK;
+    t.owner = &ch->ring;
+    t.on_device = on_device;
+    t.stage_bytes = o_tab + (on_device ? 0ull : 32ull * n_digests);
+    t.state[0] = {ch->d_h.p, 32ull * ch->n};
+    t.state[1] = {ch->d_pend.p, 32ull * ch->n};
+    t.state[2] = {ch->d_cnt.p, 8ull * ch->n};
+    t.values_out = values_out;
+    t.timer = 1;
+    return seg_submit(
+        c, t, t0,
+        [&](uint8_t* st) {
+            const uint32_t* plan = c->cm_plan.data();
+            memcpy(st, plan, 4ull * ns);
+            memcpy(st + o_first, plan + o_pfirst, 4ull * (ns + 1u));
+            memcpy(st + o_flags, plan + o_pflags, 4ull * ns);
+            memcpy(st + o_ent, plan + o_pent, 4ull * entries);
+            if (!on_device && n_digests) memcpy(st + o_tab, digests, 32ull * n_digests);
+        },
+        [&](const uint8_t* dv, const uint8_t* const* state_in, uint8_t* rows, hipStream_t q) {
+            return mirsha::launch_chains_commit_seg(
+                on_device ? digests : dv + o_tab, reinterpret_cast<const uint32_t*>(dv + o_ent),
+                reinterpret_cast<const uint32_t*>(dv), reinterpret_cast<const uint32_t*>(dv + o_first),
+                reinterpret_cast<const uint32_t*>(dv + o_flags), t.n_seg, reinterpret_cast<const uint32_t*>(state_in[0]),
+                reinterpret_cast<const uint32_t*>(state_in[1]), reinterpret_cast<const uint64_t*>(state_in[2]),
+                ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), rows, commit_seg_prio(), q);
+        },
+        n_values_out, ticket_out);
 }
 
 }  // namespace

@@ -293,6 +293,14 @@ struct mirsha_ctx {
     double prof[MIRSHA_PROF_PHASES] = {};  // host phases of the last slice submission (ms)
 };
 
+// The last segment ticket (a commit or a stream submission) queued on a state
+// object: the object's synchronous calls make their stream wait for it
+// (owner_order), its destroy waits for it (owner_retire).
+struct RingOwner {
+    hipEvent_t ev = nullptr;
+    bool queued = false;
+};
+
 // Streaming checkpoint chains (see mirsha.h, mirsha_chains_create).
 struct mirsha_chains {
     int device = 0;
@@ -303,10 +311,7 @@ struct mirsha_chains {
     // [act | efirst | ent], one H2D copy (kept across calls).
     std::vector<uint32_t> plan;
     DevBuf d_plan;
-    // The last commit submission queued on this object (mirsha_chains_commit_submit*):
-    // the synchronous calls make their stream wait for it, destroy waits for it.
-    hipEvent_t ev_commit = nullptr;
-    bool commit_queued = false;
+    RingOwner ring;  // mirsha_chains_commit_submit*
 };
 
 // Streaming hash states (see mirsha.h, mirsha_streams_create).
@@ -324,10 +329,7 @@ struct mirsha_streams {
     // form)]: ONE H2D copy.
     PinnedBuf stage;
     DevBuf dev, d_out;
-    // The last stream submission queued on this object (mirsha_streams_submit*):
-    // the synchronous calls make their stream wait for it, destroy waits for it.
-    hipEvent_t ev_run = nullptr;
-    bool run_queued = false;
+    RingOwner ring;  // mirsha_streams_submit*
 };
 
 // A request -> batch-digest pipeline plan (see mirsha.h, mirsha_pipeline_create).
@@ -429,19 +431,20 @@ struct OrderShape {
 int order_buffers(mirsha_ctx* c, uint32_t n, uint32_t bmin, uint32_t bmax, OrderShape* shape);
 int queue_bucket_order(mirsha_ctx* c, const OrderShape& shape, const uint32_t* d_len, uint32_t n, uint32_t* d_order);
 
-// Orders the context's stream behind the chains' last queued commit submission
+// Orders the context's stream behind the object's last queued segment ticket
 // (no host wait); nothing to do when there was none.
-inline int chains_order(mirsha_ctx* c, mirsha_chains* ch) {
-    if (!ch->commit_queued) return MIRSHA_OK;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, ch->ev_commit, 0));
+inline int owner_order(mirsha_ctx* c, const RingOwner& o) {
+    if (!o.queued) return MIRSHA_OK;
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, o.ev, 0));
     return MIRSHA_OK;
 }
 
-// The same for the streams' last queued stream submission.
-inline int streams_order(mirsha_ctx* c, mirsha_streams* st) {
-    if (!st->run_queued) return MIRSHA_OK;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, st->ev_run, 0));
-    return MIRSHA_OK;
+// An object's destroy: its last queued segment ticket still uses the state.
+inline void owner_retire(RingOwner& o) {
+    if (!o.ev) return;
+    (void)hipEventSynchronize(o.ev);
+    (void)hipEventDestroy(o.ev);
+    o = RingOwner{};
 }
 
 // The issue priority of the segment kernels' waves (seg_prio, mirsha_device.h).
@@ -572,6 +575,135 @@ void ring_publish(mirsha_ctx* c, AsyncSlot& sl, RingQueued& queued, const double
 uint8_t* host_rows(mirsha_ctx* c, void* p);
 // A slot's own page-locked rows, as a kernel addresses them.
 int pinned_rows(mirsha_ctx* c, const PinnedBuf& b, uint8_t** rows);
+
+// A segment ticket: a commit or a stream submission after its checks and its
+// plan (a call refused there has left the ring as it was).  What the two kinds
+// differ in, beside the callables of seg_submit:
+struct SegTicket {
+    RingOwner* owner = nullptr;
+    bool on_device = false;               // the device form: the input is read behind c->stream
+    const uint32_t* seg_flags = nullptr;  // the plan's, n_seg of them (0: nothing to queue)
+    uint32_t n_seg = 0;
+    uint64_t stage_bytes = 0;  // cm.stage's block: the ONE H2D
+    uint64_t dev_slack = 0;    // bytes of cm.dev behind the block
+    struct {
+        void* p;
+        uint64_t bytes;
+    } state[3] = {};           // the owner's state arrays: copied to cm.snap when a FIRST lane may not read them in place
+    uint8_t* values_out = nullptr;
+    uint32_t values = 0;
+    int timer = 0;  // the launch's timing id
+};
+
+// The slot lifecycle of a segment ticket, t0 = when the submitter began its
+// checks.  fill(stage) writes the staging block; launch(dev, state_in, rows, q)
+// launches the segment kernel on q: dev = the block on the device, state_in[k]
+// = state[k] or its snapshot, rows = where the values go.  Every ensure() lies
+// ahead of anything queued (a growth frees and so drains the device); a failure
+// after the first queued operation drains the commit stream (RingQueued).
+template <class Fill, class Launch>
+int seg_submit(mirsha_ctx* c, const SegTicket& t, Clock::time_point t0, Fill fill, Launch launch,
+               uint32_t* n_values_out, uint64_t* ticket_out) {
+    double ph[MIRSHA_PROF_PHASES] = {};
+    ph[MIRSHA_PROF_VALIDATE] = ms_since(t0);
+    t0 = Clock::now();
+    AsyncSlot* slot = nullptr;
+    if (int rc = ring_acquire(c, &slot)) return rc;
+    AsyncSlot& sl = *slot;
+    CommitSlot& cm = sl.cm;
+    if (t.n_seg) {
+        if (!c->xcommit) HIP_TRY(c, hipStreamCreateWithFlags(&c->xcommit, hipStreamNonBlocking));
+        if (int rc = ensure_event(c, &t.owner->ev)) return rc;
+        if (t.on_device)
+            if (int rc = ensure_event(c, &sl.ev_in)) return rc;
+    }
+    RingQueued queued(c->xcommit);
+    bool straddle = false;
+    uint8_t* rows = nullptr;
+    if (t.n_seg) {
+        straddle = mirsha::host::seg_straddle(t.seg_flags, t.n_seg, 64);
+        HIP_TRY(c, cm.stage.ensure(t.stage_bytes));
+        HIP_TRY(c, cm.dev.ensure(t.stage_bytes + t.dev_slack));
+        if (straddle) HIP_TRY(c, cm.snap.ensure(t.state[0].bytes + t.state[1].bytes + t.state[2].bytes));
+        if (t.values) {
+            // a kernel-writable values_out receives the values from the kernel
+            // itself, else the slot's rows do, copied out at retirement
+            rows = host_rows(c, t.values_out);
+            if (!rows) {
+                HIP_TRY(c, cm.rows.ensure(32ull * t.values));
+                if (int rc = pinned_rows(c, cm.rows, &rows)) return rc;
+                sl.retire.rows = SlotRows::kCommit;
+                sl.retire.out = t.values_out;
+                sl.retire.n = t.values;
+            }
+        }
+    }
+    ph[MIRSHA_PROF_PLAN] = ms_since(t0);
+    t0 = Clock::now();
+    auto queue = [&]() -> int {
+        fill(cm.stage.as<uint8_t>());
+        hipStream_t q = c->xcommit;
+        queued.arm();
+        if (t.on_device) {  // the input is read behind whatever was queued on the context's stream
+            HIP_TRY(c, hipEventRecord(sl.ev_in, c->stream));
+            HIP_TRY(c, hipStreamWaitEvent(q, sl.ev_in, 0));
+        }
+        HIP_TRY(c, hipMemcpyAsync(cm.dev.p, cm.stage.p, t.stage_bytes, hipMemcpyHostToDevice, q));
+        const uint8_t* state_in[3];
+        uint8_t* sn = cm.snap.as<uint8_t>();
+        for (int k = 0; k < 3; k++) {
+            state_in[k] = static_cast<const uint8_t*>(t.state[k].p);
+            if (!straddle || !t.state[k].bytes) continue;
+            HIP_TRY(c, hipMemcpyAsync(sn, t.state[k].p, t.state[k].bytes, hipMemcpyDeviceToDevice, q));
+            state_in[k] = sn;
+            sn += t.state[k].bytes;
+        }
+        if (int rc = timed_launch(c, t.timer, [&] { return launch(cm.dev.as<uint8_t>(), state_in, rows, q); })) return rc;
+        HIP_TRY(c, hipEventRecord(sl.done, q));
+        HIP_TRY(c, hipEventRecord(t.owner->ev, q));
+        return MIRSHA_OK;
+    };
+    if (t.n_seg) {
+        if (int rc = queue()) return rc;  // (what it queued is drained: RingQueued)
+        t.owner->queued = true;
+    }
+    sl.t_queued = Clock::now();
+    ph[MIRSHA_PROF_PACK] = ms_since(t0);
+    *n_values_out = t.values;
+    ring_publish(c, sl, queued, ph, ticket_out);
+    return MIRSHA_OK;
+}
+
+// ---- mirsha_api.hip: what mirsha_chains_commit and mirsha_chains_commit_submit
+// share of their checks.  commit_args: the argument checks of a call with ops.
+// commit_plan_failed: the message of a plan's refusal (rc, bad op).
+int commit_args(mirsha_ctx* c, const mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
+                const uint32_t* op_chain, const uint32_t* op_digest);
+int commit_plan_failed(mirsha_ctx* c, int rc, uint32_t bad, const mirsha_chains* ch, uint32_t n_digests,
+                       const uint32_t* op_chain, const uint32_t* op_digest);
+
+// ---- mirsha_streams_ring.hip: one preparation of a stream programme (n_ops > 0)
+// for mirsha_streams_run and mirsha_streams_submit.  streams_prepare: every
+// check, the plan into the object's scratch (`segments`: mirsha_stream_seg_plan
+// into seg_stream / sfirst / seg_flags, else mirsha_stream_plan into act /
+// efirst) and, host form, the packed offsets.  pack(): the entry records (16
+// bytes each) to `rec` and, host form, every distinct range's bytes to
+// `packed`.  window(): the aligned words the kernel reads, the device arena or
+// the packed bytes at d_packed.
+struct StreamPrep {
+    const uint8_t* arena = nullptr;
+    bool on_device = false;
+    uint64_t arena_len = 0;
+    uint32_t n_seg = 0, n_active = 0, entries = 0, values = 0;
+    uint64_t bytes = 0;  // host form: the packed bytes
+    const uint32_t* words = nullptr;
+    uint32_t shift = 0, span = 0;
+    void pack(mirsha_streams* st, uint8_t* rec, uint8_t* packed) const;
+    void window(const uint8_t* d_packed);
+};
+int streams_prepare(mirsha_ctx* c, mirsha_streams* st, bool segments, const uint32_t* op_stream, const uint32_t* op_kind,
+                    const uint64_t* op_off, const uint32_t* op_len, uint32_t n_ops, const uint8_t* values_out,
+                    StreamPrep* p);
 
 // ---- mirsha_plan.hip
 int plan_build(mirsha_ctx* c, mirsha_pipeline* p, uint32_t n_req, const uint32_t* idx, const uint32_t* first,

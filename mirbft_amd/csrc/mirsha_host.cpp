@@ -11,6 +11,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -853,12 +854,100 @@ extern "C" int mirsha_order_plan(uint32_t n, uint32_t min_len, uint32_t max_len,
     return MIRSHA_OK;
 }
 
+// The commit and the stream plans are one design: ops grouped by owner (chain /
+// stream), each owner's stretch cut into segments.  The shared passes are here;
+// the four entry points keep their argument checks and what an entry is.
+namespace {
+
+static_assert(MIRSHA_COMMIT_SEG_FIRST == MIRSHA_STREAM_SEG_FIRST && MIRSHA_COMMIT_SEG_LAST == MIRSHA_STREAM_SEG_LAST,
+              "one cut writes the flags of both plans");
+
+// Groups validated ops by owner: a count of each owner's kept ops, the active
+// owners and their ranges (act[k] owns entries [efirst[k], efirst[k+1])), then
+// a stable scatter in op order (a counting sort, as mirsha_chains_absorb groups
+// its writes): put(i, e) for every kept op i, e = where its entry goes.  (The
+// callers' lambdas capture their arrays by value: per op, that keeps the
+// pointers in registers across the stores.)
+template <class Owner, class Dropped, class Put>
+int group_ops(uint32_t n_ops, uint32_t n_owners, Owner owner, Dropped dropped, uint32_t* act, uint32_t* efirst,
+              uint32_t* n_active, uint32_t* n_entries, Put put) {
+    // entries of owner c, then where its next entry goes
+    const std::unique_ptr<uint32_t[]> at(new (std::nothrow) uint32_t[n_owners]());
+    if (!at) return MIRSHA_ENOMEM;
+    for (uint32_t i = 0; i < n_ops; i++)
+        if (!dropped(i)) at[owner(i)]++;
+    uint32_t na = 0, total = 0;
+    efirst[0] = 0;
+    for (uint32_t c = 0; c < n_owners; c++) {
+        const uint32_t m = at[c];
+        at[c] = total;
+        if (!m) continue;
+        act[na++] = c;
+        total += m;
+        efirst[na] = total;
+    }
+    for (uint32_t i = 0; i < n_ops; i++)
+        if (!dropped(i)) put(i, at[owner(i)]++);
+    *n_active = na;
+    *n_entries = total;
+    return MIRSHA_OK;
+}
+
+// A grouped programme cut into segments: a segment ends with an entry behind
+// which the owner restarts from Hasher() (ends_segment(e)), or with the owner's
+// final entry, so the stretches are independent hashes (one lane each).  The
+// entries stay where the grouping put them; sfirst indexes them.
+// plan(act, efirst) is the grouping entry point with its own checks; with NULL
+// it runs for its codes and its bad op only (`outputs`: no output array is NULL).
+template <class Plan, class Ends>
+int seg_plan(uint32_t n_ops, uint32_t n_owners, bool outputs, Plan plan, Ends ends_segment, uint32_t* seg_owner,
+             uint32_t* sfirst, uint32_t* seg_flags, uint32_t* n_seg, const uint32_t* n_active) {
+    *n_seg = 0;
+    if (n_ops && !outputs) {  // the argument checks of the grouping come first
+        const int rc = plan(nullptr, nullptr);
+        return rc != MIRSHA_OK ? rc : MIRSHA_EINVAL;
+    }
+    const uint32_t cap = std::min(n_ops, n_owners);  // active owners at most
+    const std::unique_ptr<uint32_t[]> act(new (std::nothrow) uint32_t[2ull * cap + 1u]());
+    if (!act) return MIRSHA_ENOMEM;
+    const uint32_t* efirst = act.get() + cap;
+    if (const int rc = plan(act.get(), act.get() + cap)) return rc;
+    if (sfirst) sfirst[0] = 0;
+    uint32_t ns = 0;
+    for (uint32_t k = 0; k < *n_active; k++) {
+        const uint32_t e0 = efirst[k], e1 = efirst[k + 1];  // e1 > e0: the owner is active
+        uint32_t start = e0;
+        for (uint32_t e = e0; e < e1; e++) {
+            if (e + 1 < e1 && !ends_segment(e)) continue;
+            seg_owner[ns] = act[k];
+            seg_flags[ns] = (start == e0 ? MIRSHA_COMMIT_SEG_FIRST : 0u) | (e + 1 == e1 ? MIRSHA_COMMIT_SEG_LAST : 0u);
+            sfirst[++ns] = e + 1;
+            start = e + 1;
+        }
+    }
+    *n_seg = ns;
+    return MIRSHA_OK;
+}
+
+}  // namespace
+
+// Segment s is lane s of the segment kernels' grid, and a wave is 64 lanes
+// whatever the workgroup size (kStreamWave for streams; 64 for the commit
+// kernel too, though its kBlockThreads is larger).  Within a wave a FIRST
+// lane's load precedes a LAST lane's store; across waves nothing orders them.
+bool mirsha::host::seg_straddle(const uint32_t* seg_flags, uint32_t n_seg, uint32_t wave_lanes) {
+    uint32_t first_wave = 0;  // of the owner whose segments are being walked
+    for (uint32_t s = 0; s < n_seg; s++) {
+        if (seg_flags[s] & MIRSHA_COMMIT_SEG_FIRST) first_wave = s / wave_lanes;
+        if ((seg_flags[s] & MIRSHA_COMMIT_SEG_LAST) && s / wave_lanes != first_wave) return true;
+    }
+    return false;
+}
+
 // A cycle's commit programme (mirsha_chains_commit) grouped by chain: a
-// validating pass (nothing is written before every op has passed), a count of
-// each chain's entries (null writes dropped), the active chains and their
-// ranges, then a stable scatter in op order (a counting sort, as
-// mirsha_chains_absorb groups its writes).  Checkpoint rows count the
-// checkpoint ops in op order across all chains.
+// validating pass (nothing is written before every op has passed), then
+// group_ops with null writes dropped.  Checkpoint rows count the checkpoint ops
+// in op order across all chains.
 extern "C" int mirsha_commit_plan(const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                   uint32_t n_chains, uint32_t n_digests, uint32_t* act_out, uint32_t* efirst_out,
                                   uint32_t* ent_out, uint32_t* n_active_out, uint32_t* n_entries_out,
@@ -881,40 +970,20 @@ extern "C" int mirsha_commit_plan(const uint32_t* op_chain, const uint32_t* op_d
         }
     }
     if (!act_out || !efirst_out || !ent_out) return MIRSHA_EINVAL;
-    std::vector<uint32_t> at;  // entries of chain c, then where its next entry goes
-    try {
-        at.assign((size_t)n_chains, 0);
-    } catch (const std::bad_alloc&) {
-        return MIRSHA_ENOMEM;
-    }
-    for (uint32_t i = 0; i < n_ops; i++)
-        if (op_digest[i] != MIRSHA_NULL_INDEX) at[op_chain[i]]++;
-    uint32_t na = 0, total = 0;
-    efirst_out[0] = 0;
-    for (uint32_t c = 0; c < n_chains; c++) {
-        const uint32_t m = at[c];
-        at[c] = total;
-        if (!m) continue;
-        act_out[na++] = c;
-        total += m;
-        efirst_out[na] = total;
-    }
     uint32_t rows = 0;
-    for (uint32_t i = 0; i < n_ops; i++) {
-        const uint32_t d = op_digest[i];
-        if (d == MIRSHA_NULL_INDEX) continue;
-        ent_out[at[op_chain[i]]++] = d == MIRSHA_COMMIT_CHECKPOINT ? (MIRSHA_COMMIT_ENTRY_CHECKPOINT | rows++) : d;
-    }
-    *n_active_out = na;
-    *n_entries_out = total;
-    *n_values_out = rows;
-    return MIRSHA_OK;
+    const int rc = group_ops(
+        n_ops, n_chains, [=](uint32_t i) { return op_chain[i]; },
+        [=](uint32_t i) { return op_digest[i] == MIRSHA_NULL_INDEX; }, act_out, efirst_out, n_active_out, n_entries_out,
+        [=, &rows](uint32_t i, uint32_t e) {
+            const uint32_t d = op_digest[i];
+            ent_out[e] = d == MIRSHA_COMMIT_CHECKPOINT ? (MIRSHA_COMMIT_ENTRY_CHECKPOINT | rows++) : d;
+        });
+    if (rc == MIRSHA_OK) *n_values_out = rows;
+    return rc;
 }
 
-// mirsha_commit_plan's per-chain programmes cut after every checkpoint entry:
-// behind a checkpoint the chain restarts from Hasher(), so the stretches are
-// independent hashes (one lane each, mirsha_chains_commit_submit).  The
-// entries stay where mirsha_commit_plan put them; sfirst indexes them.
+// mirsha_commit_plan's per-chain programmes cut after every checkpoint entry
+// (seg_plan): behind a checkpoint the chain restarts from Hasher().
 extern "C" int mirsha_commit_seg_plan(const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                       uint32_t n_chains, uint32_t n_digests, uint32_t* seg_chain_out,
                                       uint32_t* sfirst_out, uint32_t* seg_flags_out, uint32_t* ent_out,
@@ -922,40 +991,14 @@ extern "C" int mirsha_commit_seg_plan(const uint32_t* op_chain, const uint32_t* 
                                       uint32_t* n_values_out, uint32_t* bad_op_out) {
     if (bad_op_out) *bad_op_out = UINT32_MAX;
     if (!n_seg_out || !n_active_out || !n_entries_out || !n_values_out) return MIRSHA_EINVAL;
-    *n_seg_out = 0;
-    if (n_ops && (!seg_chain_out || !sfirst_out || !seg_flags_out || !ent_out)) {
-        // the argument checks of mirsha_commit_plan come first (its codes, its bad op)
-        const int rc = mirsha_commit_plan(op_chain, op_digest, n_ops, n_chains, n_digests, nullptr, nullptr, nullptr,
-                                          n_active_out, n_entries_out, n_values_out, bad_op_out);
-        return rc != MIRSHA_OK ? rc : MIRSHA_EINVAL;
-    }
-    const uint32_t cap = std::min(n_ops, n_chains);
-    std::vector<uint32_t> act, efirst;
-    try {
-        act.assign((size_t)cap, 0);
-        efirst.assign((size_t)cap + 1, 0);
-    } catch (const std::bad_alloc&) {
-        return MIRSHA_ENOMEM;
-    }
-    const int rc = mirsha_commit_plan(op_chain, op_digest, n_ops, n_chains, n_digests, act.data(), efirst.data(),
-                                      ent_out, n_active_out, n_entries_out, n_values_out, bad_op_out);
-    if (rc != MIRSHA_OK) return rc;
-    if (sfirst_out) sfirst_out[0] = 0;
-    uint32_t ns = 0;
-    for (uint32_t k = 0; k < *n_active_out; k++) {
-        const uint32_t e0 = efirst[k], e1 = efirst[k + 1];  // e1 > e0: the chain is active
-        uint32_t start = e0;
-        for (uint32_t e = e0; e < e1; e++) {
-            // a segment ends with a checkpoint entry, or with the chain's final entry
-            if (!(ent_out[e] & MIRSHA_COMMIT_ENTRY_CHECKPOINT) && e + 1 < e1) continue;
-            seg_chain_out[ns] = act[k];
-            seg_flags_out[ns] = (start == e0 ? MIRSHA_COMMIT_SEG_FIRST : 0u) | (e + 1 == e1 ? MIRSHA_COMMIT_SEG_LAST : 0u);
-            sfirst_out[++ns] = e + 1;
-            start = e + 1;
-        }
-    }
-    *n_seg_out = ns;
-    return MIRSHA_OK;
+    return seg_plan(
+        n_ops, n_chains, seg_chain_out && sfirst_out && seg_flags_out && ent_out,
+        [&](uint32_t* act, uint32_t* efirst) {
+            return mirsha_commit_plan(op_chain, op_digest, n_ops, n_chains, n_digests, act, efirst,
+                                      act ? ent_out : nullptr, n_active_out, n_entries_out, n_values_out, bad_op_out);
+        },
+        [=](uint32_t e) { return (ent_out[e] & MIRSHA_COMMIT_ENTRY_CHECKPOINT) != 0; }, seg_chain_out, sfirst_out,
+        seg_flags_out, n_seg_out, n_active_out);
 }
 
 // Where the bytes of each write entry lie among a call's packed bytes: every
@@ -988,13 +1031,11 @@ uint64_t mirsha::host::stream_pack_offsets(const uint64_t* off, const uint32_t* 
     return bytes;
 }
 
-// A call's stream programme (mirsha_streams_run) grouped by stream, as
-// mirsha_commit_plan groups a commit programme by chain: a validating pass
-// (nothing is written before every op has passed), a count of each stream's
-// entries (zero-length writes dropped), the active streams and their ranges,
-// a stable scatter in op order.  Value rows count the SUM / SUM_RESET ops in
-// op order across all streams.  With `pack` the write entries' offsets are
-// those of the packed bytes (stream_pack_offsets).
+// A call's stream programme (mirsha_streams_run) grouped by stream: a
+// validating pass (nothing is written before every op has passed), then
+// group_ops with zero-length writes dropped.  Value rows count the SUM /
+// SUM_RESET ops in op order across all streams.  With `pack` the write entries'
+// offsets are those of the packed bytes (stream_pack_offsets).
 extern "C" int mirsha_stream_plan(const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                                   const uint32_t* op_len, uint32_t n_ops, uint32_t n_streams, uint64_t arena_len,
                                   int pack, uint32_t* act_out, uint32_t* efirst_out, uint32_t* ent_kind_out,
@@ -1024,57 +1065,35 @@ extern "C" int mirsha_stream_plan(const uint32_t* op_stream, const uint32_t* op_
         }
     }
     if (!act_out || !efirst_out || !ent_kind_out || !ent_off_out || !ent_len_out) return MIRSHA_EINVAL;
-    auto dropped = [&](uint32_t i) { return op_kind[i] == MIRSHA_STREAM_WRITE && op_len[i] == 0; };
-    std::vector<uint32_t> at;  // entries of stream s, then where its next entry goes
-    try {
-        at.assign((size_t)n_streams, 0);
-    } catch (const std::bad_alloc&) {
-        return MIRSHA_ENOMEM;
-    }
-    for (uint32_t i = 0; i < n_ops; i++)
-        if (!dropped(i)) at[op_stream[i]]++;
-    uint32_t na = 0, total = 0;
-    efirst_out[0] = 0;
-    for (uint32_t s = 0; s < n_streams; s++) {
-        const uint32_t m = at[s];
-        at[s] = total;
-        if (!m) continue;
-        act_out[na++] = s;
-        total += m;
-        efirst_out[na] = total;
-    }
     uint32_t rows = 0;
-    for (uint32_t i = 0; i < n_ops; i++) {
-        if (dropped(i)) continue;
-        const uint32_t e = at[op_stream[i]]++;
-        const uint32_t k = op_kind[i];
-        const bool sum = k == MIRSHA_STREAM_SUM || k == MIRSHA_STREAM_SUM_RESET;
-        ent_kind_out[e] = k | (sum ? rows++ << 2 : 0u);
-        ent_off_out[e] = k == MIRSHA_STREAM_WRITE ? op_off[i] : 0u;
-        ent_len_out[e] = k == MIRSHA_STREAM_WRITE ? op_len[i] : 0u;
-    }
     uint64_t bytes = 0;
+    const int rc = group_ops(
+        n_ops, n_streams, [=](uint32_t i) { return op_stream[i]; },
+        [=](uint32_t i) { return op_kind[i] == MIRSHA_STREAM_WRITE && op_len[i] == 0; }, act_out, efirst_out, n_active_out,
+        n_entries_out,
+        [=, &rows, &bytes](uint32_t i, uint32_t e) {
+            const uint32_t k = op_kind[i];
+            const bool sum = k == MIRSHA_STREAM_SUM || k == MIRSHA_STREAM_SUM_RESET;
+            ent_kind_out[e] = k | (sum ? rows++ << 2 : 0u);
+            ent_off_out[e] = k == MIRSHA_STREAM_WRITE ? op_off[i] : 0u;
+            bytes += ent_len_out[e] = k == MIRSHA_STREAM_WRITE ? op_len[i] : 0u;
+        });
+    if (rc != MIRSHA_OK) return rc;
     if (pack) {
         try {
-            bytes = mirsha::host::stream_pack_offsets(ent_off_out, ent_len_out, total, ent_off_out);
+            bytes = mirsha::host::stream_pack_offsets(ent_off_out, ent_len_out, *n_entries_out, ent_off_out);
         } catch (const std::bad_alloc&) {
+            *n_active_out = *n_entries_out = 0;
             return MIRSHA_ENOMEM;
         }
-    } else {
-        for (uint32_t e = 0; e < total; e++) bytes += ent_len_out[e];
     }
-    *n_active_out = na;
-    *n_entries_out = total;
     *n_values_out = rows;
     *n_bytes_out = bytes;
     return MIRSHA_OK;
 }
 
 // mirsha_stream_plan's per-stream programmes cut after every SUM_RESET and
-// RESET entry, as mirsha_commit_seg_plan cuts a chain's after every
-// checkpoint: behind either the stream restarts from Hasher(), so the
-// stretches are independent hashes (one lane each, mirsha_streams_submit).
-// The entries stay where mirsha_stream_plan put them; sfirst indexes them.
+// RESET entry (seg_plan): behind either the stream restarts from Hasher().
 extern "C" int mirsha_stream_seg_plan(const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                                       const uint32_t* op_len, uint32_t n_ops, uint32_t n_streams, uint64_t arena_len,
                                       int pack, uint32_t* seg_stream_out, uint32_t* sfirst_out,
@@ -1084,42 +1103,19 @@ extern "C" int mirsha_stream_seg_plan(const uint32_t* op_stream, const uint32_t*
                                       uint32_t* bad_op_out) {
     if (bad_op_out) *bad_op_out = UINT32_MAX;
     if (!n_seg_out || !n_active_out || !n_entries_out || !n_values_out || !n_bytes_out) return MIRSHA_EINVAL;
-    *n_seg_out = 0;
-    if (n_ops && (!seg_stream_out || !sfirst_out || !seg_flags_out || !ent_kind_out || !ent_off_out || !ent_len_out)) {
-        // the argument checks of mirsha_stream_plan come first (its codes, its bad op)
-        const int rc = mirsha_stream_plan(op_stream, op_kind, op_off, op_len, n_ops, n_streams, arena_len, pack,
-                                          nullptr, nullptr, nullptr, nullptr, nullptr, n_active_out, n_entries_out,
-                                          n_values_out, n_bytes_out, bad_op_out);
-        return rc != MIRSHA_OK ? rc : MIRSHA_EINVAL;
-    }
-    const uint32_t cap = std::min(n_ops, n_streams);
-    std::vector<uint32_t> act, efirst;
-    try {
-        act.assign((size_t)cap, 0);
-        efirst.assign((size_t)cap + 1, 0);
-    } catch (const std::bad_alloc&) {
-        return MIRSHA_ENOMEM;
-    }
-    const int rc = mirsha_stream_plan(op_stream, op_kind, op_off, op_len, n_ops, n_streams, arena_len, pack, act.data(),
-                                      efirst.data(), ent_kind_out, ent_off_out, ent_len_out, n_active_out,
-                                      n_entries_out, n_values_out, n_bytes_out, bad_op_out);
-    if (rc != MIRSHA_OK) return rc;
-    if (sfirst_out) sfirst_out[0] = 0;
-    uint32_t ns = 0;
-    for (uint32_t k = 0; k < *n_active_out; k++) {
-        const uint32_t e0 = efirst[k], e1 = efirst[k + 1];  // e1 > e0: the stream is active
-        uint32_t start = e0;
-        for (uint32_t e = e0; e < e1; e++) {
-            // a segment ends with an entry that leaves Hasher(), or with the stream's final entry
+    return seg_plan(
+        n_ops, n_streams,
+        seg_stream_out && sfirst_out && seg_flags_out && ent_kind_out && ent_off_out && ent_len_out,
+        [&](uint32_t* act, uint32_t* efirst) {
+            return mirsha_stream_plan(op_stream, op_kind, op_off, op_len, n_ops, n_streams, arena_len, pack, act, efirst,
+                                      act ? ent_kind_out : nullptr, act ? ent_off_out : nullptr,
+                                      act ? ent_len_out : nullptr, n_active_out, n_entries_out, n_values_out,
+                                      n_bytes_out, bad_op_out);
+        },
+        [=](uint32_t e) {
             const uint32_t kind = ent_kind_out[e] & 3u;
-            if (kind != MIRSHA_STREAM_SUM_RESET && kind != MIRSHA_STREAM_RESET && e + 1 < e1) continue;
-            seg_stream_out[ns] = act[k];
-            seg_flags_out[ns] =
-                (start == e0 ? MIRSHA_STREAM_SEG_FIRST : 0u) | (e + 1 == e1 ? MIRSHA_STREAM_SEG_LAST : 0u);
-            sfirst_out[++ns] = e + 1;
-            start = e + 1;
-        }
-    }
-    *n_seg_out = ns;
-    return MIRSHA_OK;
+            return kind == MIRSHA_STREAM_SUM_RESET || kind == MIRSHA_STREAM_RESET;
+        },
+        seg_stream_out, sfirst_out, seg_flags_out, n_seg_out, n_active_out);
 }
+

@@ -137,6 +137,12 @@ uint32_t order_chunk(uint32_t bins);
 // equals the bytes packed before it.  poff_out may be `off` itself.
 uint64_t stream_pack_offsets(const uint64_t* off, const uint32_t* len, uint32_t entries, uint64_t* poff_out);
 
+// A segment plan's flags (mirsha_commit_seg_plan / mirsha_stream_seg_plan),
+// segment s being lane s of a grid of `wave_lanes`-lane waves: does some
+// owner's LAST segment lie in another wave than its FIRST?  The submitter then
+// passes the FIRST lanes a copy of the states taken ahead of the launch.
+bool seg_straddle(const uint32_t* seg_flags, uint32_t n_seg, uint32_t wave_lanes);
+
 // Copies request which[k] (k < m) to dst + dst_off[k], in parallel.  With
 // `stream` the stores bypass the CPU caches (non-temporal, fenced before
 // return): for page-locked staging a DMA reads next, which then runs at the

@@ -65,85 +65,36 @@ int streams_run(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, bool on
     if (!c || !st || !n_values_out) return MIRSHA_EINVAL;
     *n_values_out = 0;
     if (n_ops == 0) return MIRSHA_OK;
-    if (!op_stream || !op_kind) return fail(c, MIRSHA_EINVAL, "NULL argument");
-    if (st->device != c->device) return fail(c, MIRSHA_EINVAL, "streams belong to another device");
-    if (on_device && arena_len > MIRSHA_MAX_DEVICE_ARENA_BYTES)
-        return fail(c, MIRSHA_ERANGE, "device arena of %llu bytes > %u", (unsigned long long)arena_len,
-                    MIRSHA_MAX_DEVICE_ARENA_BYTES);
-    const uint32_t cap = std::min(n_ops, st->n);
-    st->act.resize(cap);
-    st->efirst.resize((size_t)cap + 1u);
-    st->kind.resize(n_ops);
-    st->len.resize(n_ops);
-    st->off.resize(n_ops);
-    uint32_t na = 0, entries = 0, values = 0, bad = UINT32_MAX;
-    uint64_t bytes = 0;
-    const int rc = mirsha_stream_plan(op_stream, op_kind, op_off, op_len, n_ops, st->n, arena_len, 0, st->act.data(),
-                                      st->efirst.data(), st->kind.data(), st->off.data(), st->len.data(), &na,
-                                      &entries, &values, &bytes, &bad);
-    if (rc == MIRSHA_ERANGE) return fail(c, rc, "%u ops > %u", n_ops, MIRSHA_STREAM_MAX_OPS);
-    if (rc != MIRSHA_OK) {
-        if (bad == UINT32_MAX) return fail(c, rc, "stream plan failed (a NULL op array?)");
-        if (op_stream[bad] >= st->n) return fail(c, rc, "op_stream[%u] = %u >= %u", bad, op_stream[bad], st->n);
-        if (op_kind[bad] > MIRSHA_STREAM_RESET) return fail(c, rc, "op_kind[%u] = %u is no kind", bad, op_kind[bad]);
-        return fail(c, rc, "op %u writes [%llu, +%u) of an arena of %llu bytes", bad, (unsigned long long)op_off[bad],
-                    op_len[bad], (unsigned long long)arena_len);
-    }
-    if (bytes && !arena) return fail(c, MIRSHA_EINVAL, "NULL arena (%llu bytes to write)", (unsigned long long)bytes);
-    if (values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u sums)", values);
-    if (!on_device) {  // what crosses PCIe: every distinct range once (mirsha_stream_plan, pack)
-        st->poff.resize(n_ops);
-        bytes = mirsha::host::stream_pack_offsets(st->off.data(), st->len.data(), entries, st->poff.data());
-        if (bytes + kArenaSlack > MIRSHA_MAX_DEVICE_ARENA_BYTES)
-            return fail(c, MIRSHA_ERANGE, "%llu written bytes > %u", (unsigned long long)bytes,
-                        MIRSHA_MAX_DEVICE_ARENA_BYTES - (uint32_t)kArenaSlack);
-    }
+    StreamPrep p;
+    p.arena = arena, p.on_device = on_device, p.arena_len = arena_len;
+    if (int r = streams_prepare(c, st, false, op_stream, op_kind, op_off, op_len, n_ops, values_out, &p)) return r;
+    const uint32_t na = p.n_active;
     if (na == 0) return MIRSHA_OK;  // zero-length writes only
     if (int r = use_device(c)) return r;
-    if (int r = streams_order(c, st)) return r;
-    const uint64_t o_first = 4ull * na, o_ent = align16(o_first + 4ull * (na + 1u)), o_bytes = o_ent + 16ull * entries;
-    const uint64_t h2d = o_bytes + (on_device ? 0ull : bytes);
+    if (int r = owner_order(c, st->ring)) return r;
+    // [act | efirst | pad to 16 | entry records | packed bytes (host form)]
+    const uint64_t o_first = 4ull * na, o_ent = align16(o_first + 4ull * (na + 1u)), o_bytes = o_ent + 16ull * p.entries;
+    const uint64_t h2d = o_bytes + (on_device ? 0ull : p.bytes);
     HIP_TRY(c, st->stage.ensure(h2d));
     HIP_TRY(c, st->dev.ensure(h2d + kArenaSlack));  // the last word of the bytes lies inside
-    HIP_TRY(c, st->d_out.ensure(32ull * std::max(values, 1u)));
+    HIP_TRY(c, st->d_out.ensure(32ull * std::max(p.values, 1u)));
     uint8_t* sg = st->stage.as<uint8_t>();
-    if (!on_device) {
-        uint64_t at = 0;
-        for (uint32_t e = 0; e < entries; e++) {
-            if (st->len[e] && st->poff[e] == at) {  // the range's first entry: its bytes go in here
-                memcpy(sg + o_bytes + at, arena + st->off[e], st->len[e]);
-                at += st->len[e];
-            }
-            st->off[e] = st->poff[e];
-        }
-    }
+    p.pack(st, sg + o_ent, sg + o_bytes);
     memcpy(sg, st->act.data(), 4ull * na);
     memcpy(sg + o_first, st->efirst.data(), 4ull * (na + 1u));
-    uint32_t* rec = reinterpret_cast<uint32_t*>(sg + o_ent);  // the plan's entry arrays, one 16-byte record each
-    for (uint32_t e = 0; e < entries; e++) {
-        rec[4ull * e] = st->kind[e];
-        rec[4ull * e + 1] = st->len[e];
-        rec[4ull * e + 2] = (uint32_t)st->off[e];
-        rec[4ull * e + 3] = (uint32_t)(st->off[e] >> 32);
-    }
     HIP_TRY(c, hipMemcpyAsync(st->dev.p, sg, h2d, hipMemcpyHostToDevice, c->stream));
     const uint8_t* dv = st->dev.as<uint8_t>();
-    // aligned words only: a word never crosses a page, so the up to 3 bytes
-    // beside a device arena that share a word with it are safe to load
-    const uintptr_t base = on_device ? reinterpret_cast<uintptr_t>(arena) : reinterpret_cast<uintptr_t>(dv + o_bytes);
-    const uint32_t shift = (uint32_t)(base & 3u);
-    const uint64_t extent = on_device ? arena_len : bytes;
-    const uint32_t span = extent ? (uint32_t)((shift + extent + 3u) & ~3ull) : 0u;
+    p.window(dv + o_bytes);
     if (int r = timed_launch(c, kTimerStreams, [&] {
-            return mirsha::launch_streams(
-                reinterpret_cast<const uint32_t*>(base - shift), shift, span, reinterpret_cast<const uint32_t*>(dv),
-                reinterpret_cast<const uint32_t*>(dv + o_ent), na,
-                st->d_state.as<uint8_t>(), st->d_out.as<uint8_t>(), c->stream);
+            return mirsha::launch_streams(p.words, p.shift, p.span, reinterpret_cast<const uint32_t*>(dv),
+                                          reinterpret_cast<const uint32_t*>(dv + o_ent), na, st->d_state.as<uint8_t>(),
+                                          st->d_out.as<uint8_t>(), c->stream);
         }))
         return r;
-    if (values) HIP_TRY(c, hipMemcpyAsync(values_out, st->d_out.p, 32ull * values, hipMemcpyDeviceToHost, c->stream));
+    if (p.values)
+        HIP_TRY(c, hipMemcpyAsync(values_out, st->d_out.p, 32ull * p.values, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *n_values_out = values;
+    *n_values_out = p.values;
     return MIRSHA_OK;
 }
 
@@ -190,10 +141,7 @@ int mirsha_streams_create(mirsha_ctx* c, uint32_t n, mirsha_streams** out) {
 void mirsha_streams_destroy(mirsha_streams* st) {
     if (!st) return;
     (void)hipSetDevice(st->device);
-    if (st->ev_run) {  // the last queued stream submission still uses the state
-        (void)hipEventSynchronize(st->ev_run);
-        (void)hipEventDestroy(st->ev_run);
-    }
+    owner_retire(st->ring);
     for (DevBuf* b : {&st->d_state, &st->dev, &st->d_out}) b->release();
     st->stage.release();
     delete st;
@@ -217,7 +165,7 @@ int mirsha_streams_export(mirsha_ctx* c, mirsha_streams* st, const uint32_t* whi
     if (!c || !st) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (int rc = streams_which(c, st, which, k, out)) return rc;
-    if (int rc = streams_order(c, st)) return rc;
+    if (int rc = owner_order(c, st->ring)) return rc;
     std::vector<uint32_t> rows((size_t)kRowWords * k);
     for (uint32_t j = 0; j < k; j++)
         HIP_TRY(c, hipMemcpyAsync(&rows[(size_t)kRowWords * j], st->d_state.as<uint32_t>() + (uint64_t)kRowWords * which[j],
@@ -241,7 +189,7 @@ int mirsha_streams_import(mirsha_ctx* c, mirsha_streams* st, const uint32_t* whi
     if (!c || !st) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (int rc = streams_which(c, st, which, k, in)) return rc;
-    if (int rc = streams_order(c, st)) return rc;
+    if (int rc = owner_order(c, st->ring)) return rc;
     for (uint32_t j = 0; j < k; j++)
         if (memcmp(in + (uint64_t)kStateBytes * j, kStateMagic, 4) != 0)
             return fail(c, MIRSHA_EINVAL, "state %u does not begin with \"sha\\x03\"", j);

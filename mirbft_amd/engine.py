@@ -134,26 +134,26 @@ class ExpectTicket(Ticket):
         self.mismatches = np.union1d(bad, self._short) if self._short.size else bad
 
 
-class CommitTicket(Ticket):
-    """A submission of CheckpointChains.submit_commit / submit_commit_device.
-    ``values`` (= ``out``), shape (k, 32): one row per checkpoint op, in op
-    order; complete after ``Engine.wait`` (or a ``poll`` that reports done)."""
+class ValuesTicket(Ticket):
+    """A segment ticket: a programme over device-resident hash states.
+    ``values`` (= ``out``), shape (k, 32): one row per op that yields a value,
+    in op order; complete after ``Engine.wait`` (or a ``poll`` that reports
+    done)."""
 
     @property
     def values(self) -> np.ndarray:
         return self.out
 
 
-class StreamTicket(Ticket):
-    """A submission of HashStreams.submit / submit_device / submit_flush.
-    ``values`` (= ``out``), shape (k, 32): one row per STREAM_SUM /
-    STREAM_SUM_RESET op, in op order; complete after ``Engine.wait`` (or a
-    ``poll`` that reports done).  A ``submit_flush`` ticket's rows are in the
-    order of its hashers."""
+class CommitTicket(ValuesTicket):
+    """A submission of CheckpointChains.submit_commit / submit_commit_device:
+    one row per checkpoint op."""
 
-    @property
-    def values(self) -> np.ndarray:
-        return self.out
+
+class StreamTicket(ValuesTicket):
+    """A submission of HashStreams.submit / submit_device / submit_flush: one
+    row per STREAM_SUM / STREAM_SUM_RESET op.  A ``submit_flush`` ticket's rows
+    are in the order of its hashers."""
 
 
 def _out_rows(out, n: int) -> np.ndarray:
@@ -828,12 +828,52 @@ class Pipeline:
             pass
 
 
-class CheckpointChains:
+class _StateObject:
+    """What CheckpointChains and HashStreams share: hash states on the device
+    (``handle``, of ``_engine``) whose programmes run in one call or as a
+    ValuesTicket of the engine's ring."""
+
+    _VALUES = ("", "")  # the count check's message: the call, what yields a value
+    _DESTROY = ""
+
+    def _values(self, call, args, n: int, out=None, keep=None, ticket=None):
+        """call(ctx, handle, *args, out, &count[, &ticket]) for a programme with
+        ``n`` value ops, and the count check.  Without ``ticket`` (a
+        ValuesTicket class) the call is synchronous and the (n, 32) values are
+        returned; with it the ticket is, and until it retires it keeps
+        ``out``, ``keep`` and this object (the kernel writes its state)."""
+        out = _out_rows(out, n)
+        k, t = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        eng = self._engine
+        eng._check(call(eng.ctx, self.handle, *args, _ptr(out), ctypes.byref(k), *([ctypes.byref(t)] if ticket else [])))
+        if k.value != n:
+            raise MirshaError(_lib.MIRSHA_EHIP, f"{self._VALUES[0]}: {k.value} values for {n} {self._VALUES[1]}")
+        if ticket is None:
+            return out
+        eng._outstanding[t.value] = (out, keep, self)
+        eng._retire(t.value - ASYNC_SLOTS)
+        return ticket(t.value, out)
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            getattr(self._lib, self._DESTROY)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CheckpointChains(_StateObject):
     """Streaming checkpoint chains on the device (mirsha_chains_*): one running
     SHA-256 per application node, as testengine's NodeState.ActiveHash
     (testengine/recorder.go:186-256).  write() = ActiveHash.Write of committed
     request digests, sum() = ActiveHash.Sum(nil) (state unchanged),
     reset() = NodeState.Set's fresh hasher."""
+
+    _VALUES, _DESTROY = ("commit", "checkpoints"), "mirsha_chains_destroy"
 
     def __init__(self, engine: Engine, n_chains: int):
         self._engine = engine
@@ -881,15 +921,11 @@ class CheckpointChains:
         return self._commit(self._lib.mirsha_chains_commit_device, int(d_digests) or None, int(n_digests), op_chain,
                             op_digest)
 
-    def _commit(self, call, table, n_digests: int, op_chain, op_digest) -> np.ndarray:
+    def _commit(self, call, table, n_digests: int, op_chain, op_digest, *ring):
+        """``ring``: (out, keep, CommitTicket) of a submission."""
         oc, od = _commit_ops(op_chain, op_digest)
-        out = np.empty((int(np.count_nonzero(od == _lib.MIRSHA_COMMIT_CHECKPOINT)), 32), dtype=np.uint8)
-        k = ctypes.c_uint32(0)
-        self._engine._check(call(self._engine.ctx, self.handle, table, n_digests, _ptr(oc), _ptr(od), oc.size,
-                                 _ptr(out), ctypes.byref(k)))
-        if k.value != out.shape[0]:
-            raise MirshaError(_lib.MIRSHA_EHIP, f"commit: {k.value} values for {out.shape[0]} checkpoints")
-        return out
+        return self._values(call, (table, n_digests, _ptr(oc), _ptr(od), oc.size),
+                            int(np.count_nonzero(od == _lib.MIRSHA_COMMIT_CHECKPOINT)), *ring)
 
     def submit_commit(self, digests, op_chain, op_digest, out=None) -> "CommitTicket":
         """commit() as a submission of the engine's ring
@@ -901,8 +937,8 @@ class CheckpointChains:
         page-locked ``out`` (``engine.host_empty``) receives the values from
         the kernel itself."""
         d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
-        return self._submit(self._lib.mirsha_chains_commit_submit, _ptr(d), d.shape[0], op_chain, op_digest, out,
-                            None)
+        return self._commit(self._lib.mirsha_chains_commit_submit, _ptr(d), d.shape[0], op_chain, op_digest, out,
+                            None, CommitTicket)
 
     def submit_commit_device(self, d_digests: int, n_digests: int, op_chain, op_digest, out=None,
                              keep=None) -> "CommitTicket":
@@ -911,32 +947,8 @@ class CheckpointChains:
         engine's stream at this moment, e.g. the ``hash_batch_device`` that
         writes it, and must stay intact until the ticket retires (``keep``:
         an object to hold on to until then)."""
-        return self._submit(self._lib.mirsha_chains_commit_submit_device, int(d_digests) or None, int(n_digests),
-                            op_chain, op_digest, out, keep)
-
-    def _submit(self, call, table, n_digests: int, op_chain, op_digest, out, keep) -> "CommitTicket":
-        oc, od = _commit_ops(op_chain, op_digest)
-        out = _out_rows(out, int(np.count_nonzero(od == _lib.MIRSHA_COMMIT_CHECKPOINT)))
-        k, t = ctypes.c_uint32(0), ctypes.c_uint64(0)
-        eng = self._engine
-        eng._check(call(eng.ctx, self.handle, table, n_digests, _ptr(oc), _ptr(od), oc.size, _ptr(out),
-                        ctypes.byref(k), ctypes.byref(t)))
-        if k.value != out.shape[0]:
-            raise MirshaError(_lib.MIRSHA_EHIP, f"commit: {k.value} values for {out.shape[0]} checkpoints")
-        eng._outstanding[t.value] = (out, keep, self)  # the chains too: the kernel writes their state
-        eng._retire(t.value - ASYNC_SLOTS)
-        return CommitTicket(t.value, out)
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self._lib.mirsha_chains_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._commit(self._lib.mirsha_chains_commit_submit_device, int(d_digests) or None, int(n_digests),
+                            op_chain, op_digest, out, keep, CommitTicket)
 
 
 def _stream_ops(ops) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
@@ -1021,7 +1033,7 @@ def stream_seg_plan(ops, n_streams: int, arena_len: int, pack: bool = False):
             ln[:ne.value], nv.value, nb.value, na.value)
 
 
-class HashStreams:
+class HashStreams(_StateObject):
     """Streaming SHA-256 states on the device (mirsha_streams_*): n hashers in
     the reference's own shape, ``type Hasher func() hash.Hash``
     (processor.go:21) -- Write any bytes any number of times, Sum at any point
@@ -1033,6 +1045,8 @@ class HashStreams:
     resets, beside the hashing).  ``bytes_sent`` counts the bytes of the
     distinct ranges the write ops of each ``run`` / ``submit`` named (what
     crossed PCIe); ``runs`` the calls."""
+
+    _VALUES, _DESTROY = ("streams", "sums"), "mirsha_streams_destroy"
 
     def __init__(self, engine: Engine, n_streams: int):
         self._engine = engine
@@ -1058,17 +1072,14 @@ class HashStreams:
         engine's stream."""
         return self._run(self._lib.mirsha_streams_run_device, int(d_arena) or None, int(arena_len), ops)
 
-    def _run(self, call, arena, arena_len: int, ops) -> np.ndarray:
+    def _run(self, call, arena, arena_len: int, ops, *ring):
+        """``ring``: (out, keep, StreamTicket) of a submission."""
         os_, ok, oo, ol = _stream_ops(ops)
         sums = (ok == _lib.MIRSHA_STREAM_SUM) | (ok == _lib.MIRSHA_STREAM_SUM_RESET)
-        out = np.empty((int(np.count_nonzero(sums)), 32), dtype=np.uint8)
-        k = ctypes.c_uint32(0)
-        self._engine._check(call(self._engine.ctx, self.handle, arena, arena_len, _ptr(os_), _ptr(ok), _ptr(oo),
-                                 _ptr(ol), os_.size, _ptr(out), ctypes.byref(k)))
-        if k.value != out.shape[0]:
-            raise MirshaError(_lib.MIRSHA_EHIP, f"streams: {k.value} values for {out.shape[0]} sums")
-        self._count(call is self._lib.mirsha_streams_run, ok, oo, ol)
-        return out
+        got = self._values(call, (arena, arena_len, _ptr(os_), _ptr(ok), _ptr(oo), _ptr(ol), os_.size),
+                           int(np.count_nonzero(sums)), *ring)
+        self._count(call in (self._lib.mirsha_streams_run, self._lib.mirsha_streams_submit), ok, oo, ol)
+        return got
 
     def _count(self, host: bool, ok, oo, ol) -> None:
         if host:  # every distinct (off, len) range once: a sort and a compare with the neighbour
@@ -1091,7 +1102,7 @@ class HashStreams:
         ``out`` (``engine.host_empty``) receives the values from the kernel
         itself."""
         a = _as_u8(arena)
-        return self._submit(self._lib.mirsha_streams_submit, _ptr(a), a.size, ops, out, None)
+        return self._run(self._lib.mirsha_streams_submit, _ptr(a), a.size, ops, out, None, StreamTicket)
 
     def submit_device(self, ops, d_arena: int, arena_len: int, out=None, keep=None) -> "StreamTicket":
         """submit() with the arena in device memory (a raw device address, any
@@ -1099,23 +1110,8 @@ class HashStreams:
         stream at this moment, e.g. the ``hash_batch_device`` that writes it,
         and must stay intact until the ticket retires (``keep``: an object to
         hold on to until then)."""
-        return self._submit(self._lib.mirsha_streams_submit_device, int(d_arena) or None, int(arena_len), ops, out,
-                            keep)
-
-    def _submit(self, call, arena, arena_len: int, ops, out, keep) -> "StreamTicket":
-        os_, ok, oo, ol = _stream_ops(ops)
-        sums = (ok == _lib.MIRSHA_STREAM_SUM) | (ok == _lib.MIRSHA_STREAM_SUM_RESET)
-        out = _out_rows(out, int(np.count_nonzero(sums)))
-        k, t = ctypes.c_uint32(0), ctypes.c_uint64(0)
-        eng = self._engine
-        eng._check(call(eng.ctx, self.handle, arena, arena_len, _ptr(os_), _ptr(ok), _ptr(oo), _ptr(ol), os_.size,
-                        _ptr(out), ctypes.byref(k), ctypes.byref(t)))
-        if k.value != out.shape[0]:
-            raise MirshaError(_lib.MIRSHA_EHIP, f"streams: {k.value} values for {out.shape[0]} sums")
-        self._count(call is self._lib.mirsha_streams_submit, ok, oo, ol)
-        eng._outstanding[t.value] = (out, keep, self)  # the streams too: the kernel writes their state
-        eng._retire(t.value - ASYNC_SLOTS)
-        return StreamTicket(t.value, out)
+        return self._run(self._lib.mirsha_streams_submit_device, int(d_arena) or None, int(arena_len), ops, out,
+                         keep, StreamTicket)
 
     def export_state(self, which) -> np.ndarray:
         """The states of streams ``which`` as (k, 108) uint8 rows in the layout
@@ -1186,17 +1182,6 @@ class HashStreams:
             if sums:
                 ops.append((hs.stream, _lib.MIRSHA_STREAM_SUM, 0, 0))
         return ops, b"".join(parts)
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self._lib.mirsha_streams_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class StreamHasher:

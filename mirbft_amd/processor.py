@@ -136,6 +136,13 @@ class ActionResults:
     checkpoints: list = field(default_factory=list)
 
 
+def _is_checkpoint(k: int, commit) -> bool:
+    """Which of its two kinds commits[k] is."""
+    if (commit.batch is None) == (commit.checkpoint is None):
+        raise ValueError(f"commits[{k}]: exactly one of batch and checkpoint must be set")
+    return commit.checkpoint is not None
+
+
 def commit_programme(commits, n_nodes: int = 1):
     """Host-only: one cycle's ``actions.commits`` as the arguments of
     ``CheckpointChains.commit`` for nodes 0..n_nodes-1, which all commit the
@@ -147,9 +154,7 @@ def commit_programme(commits, n_nodes: int = 1):
     on that node."""
     rows, prog = [], []
     for k, commit in enumerate(commits):
-        if (commit.batch is None) == (commit.checkpoint is None):
-            raise ValueError(f"commits[{k}]: exactly one of batch and checkpoint must be set")
-        if commit.checkpoint is not None:
+        if _is_checkpoint(k, commit):
             prog.append(MIRSHA_COMMIT_CHECKPOINT)
             continue
         for d in commit.batch.digests:
@@ -166,7 +171,42 @@ def commit_programme(commits, n_nodes: int = 1):
     return table, op_chain, op_digest
 
 
-class DeviceLog:
+class _CycleLog:
+    """What ``DeviceLog`` and ``StreamLog`` share: one cycle's
+    ``actions.commits`` as ONE programme over a state object on the device (one
+    state per node), run in one call or as a ticket of the engine's ring.  A
+    subclass gives ``_cycle(commits)``, the arguments of its ``_run`` /
+    ``_submit`` (the state object's synchronous and ring call)."""
+
+    def __init__(self, engine: Engine, n_nodes: int, node: int, state, make):
+        if not 0 <= node < n_nodes:
+            raise ValueError(f"node {node} of {n_nodes}")
+        self._engine = engine
+        self.n_nodes, self.node = int(n_nodes), int(node)
+        self._state = state if state is not None else make(engine, self.n_nodes)
+        self.values = np.empty((0, self.n_nodes, 32), dtype=np.uint8)
+
+    def _node_values(self, rows) -> list:
+        self.values = rows.reshape(-1, self.n_nodes, 32)
+        return [v.tobytes() for v in self.values[:, self.node]]
+
+    def commit_cycle(self, commits) -> list:
+        return self._node_values(self._run(*self._cycle(commits)))
+
+    def submit_cycle(self, commits):
+        """Queues one cycle's commits; returns the ticket ``collect_cycle`` takes."""
+        return self._submit(*self._cycle(commits))
+
+    def collect_cycle(self, ticket) -> list:
+        """Waits for a cycle queued by ``submit_cycle``: node ``node``'s value
+        per checkpoint, in commit order; ``values`` holds every node's."""
+        return self._node_values(self._engine.wait(ticket))
+
+    def close(self) -> None:
+        self._state.close()
+
+
+class DeviceLog(_CycleLog):
     """The application log of a Processor on the device: it stands where
     ``p.Log.Apply`` and ``p.Log.Snap`` stand in the commit loop
     (processor.go:147,163), with the testengine application's state
@@ -184,31 +224,12 @@ class DeviceLog:
     they are collected in."""
 
     def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, chains=None):
-        if not 0 <= node < n_nodes:
-            raise ValueError(f"node {node} of {n_nodes}")
-        self._engine = engine
-        self.n_nodes, self.node = int(n_nodes), int(node)
-        self.chains = chains if chains is not None else CheckpointChains(engine, self.n_nodes)
-        self.values = np.empty((0, self.n_nodes, 32), dtype=np.uint8)
+        super().__init__(engine, n_nodes, node, chains, CheckpointChains)
+        self.chains = self._state
+        self._run, self._submit = self.chains.commit, self.chains.submit_commit
 
-    def commit_cycle(self, commits) -> list:
-        table, op_chain, op_digest = commit_programme(commits, self.n_nodes)
-        self.values = self.chains.commit(table, op_chain, op_digest).reshape(-1, self.n_nodes, 32)
-        return [v.tobytes() for v in self.values[:, self.node]]
-
-    def submit_cycle(self, commits):
-        """Queues one cycle's commits; returns the ticket ``collect_cycle`` takes."""
-        table, op_chain, op_digest = commit_programme(commits, self.n_nodes)
-        return self.chains.submit_commit(table, op_chain, op_digest)
-
-    def collect_cycle(self, ticket) -> list:
-        """Waits for a cycle queued by ``submit_cycle``: node ``node``'s value
-        per checkpoint, in commit order; ``values`` holds every node's."""
-        self.values = self._engine.wait(ticket).reshape(-1, self.n_nodes, 32)
-        return [v.tobytes() for v in self.values[:, self.node]]
-
-    def close(self) -> None:
-        self.chains.close()
+    def _cycle(self, commits):
+        return commit_programme(commits, self.n_nodes)
 
 
 def batch_digests(batch) -> list:
@@ -224,7 +245,7 @@ def batch_digests(batch) -> list:
     return out
 
 
-class StreamLog:
+class StreamLog(_CycleLog):
     """``DeviceLog``'s interface over ``HashStreams``: an application log whose
     ``Apply`` writes ANY bytes (Log.Apply(*pb.QEntry) / Log.Snap are
     application-defined, processor.go:28-31), e.g. sequence numbers, payloads
@@ -242,21 +263,16 @@ class StreamLog:
     ``DeviceLog`` stays the log for digest-only applications."""
 
     def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, entry_data=None, streams=None):
-        if not 0 <= node < n_nodes:
-            raise ValueError(f"node {node} of {n_nodes}")
-        self._engine = engine
-        self.n_nodes, self.node = int(n_nodes), int(node)
+        super().__init__(engine, n_nodes, node, streams, HashStreams)
         self.entry_data = entry_data if entry_data is not None else batch_digests
-        self.streams = streams if streams is not None else HashStreams(engine, self.n_nodes)
-        self.values = np.empty((0, self.n_nodes, 32), dtype=np.uint8)
+        self.streams = self._state
+        self._run, self._submit = self.streams.run, self.streams.submit
 
     def cycle_programme(self, commits):
         """Host-only: (ops, arena) of one cycle for ``HashStreams.run``."""
         kinds, offs, lens, parts, at = [], [], [], [], 0
         for k, commit in enumerate(commits):
-            if (commit.batch is None) == (commit.checkpoint is None):
-                raise ValueError(f"commits[{k}]: exactly one of batch and checkpoint must be set")
-            if commit.checkpoint is not None:
+            if _is_checkpoint(k, commit):
                 kinds.append(STREAM_SUM_RESET), offs.append(0), lens.append(0)
                 continue
             data = b"".join(bytes(d) for d in self.entry_data(commit.batch))
@@ -268,25 +284,7 @@ class StreamLog:
                np.repeat(np.asarray(offs, dtype=np.uint64), n), np.repeat(np.asarray(lens, dtype=np.uint32), n))
         return ops, b"".join(parts)
 
-    def commit_cycle(self, commits) -> list:
-        ops, arena = self.cycle_programme(commits)
-        self.values = self.streams.run(ops, arena).reshape(-1, self.n_nodes, 32)
-        return [v.tobytes() for v in self.values[:, self.node]]
-
-    def submit_cycle(self, commits):
-        """Queues one cycle's commits (``HashStreams.submit``, a ticket of the
-        engine's ring); returns the ticket ``collect_cycle`` takes."""
-        ops, arena = self.cycle_programme(commits)
-        return self.streams.submit(ops, arena)
-
-    def collect_cycle(self, ticket) -> list:
-        """Waits for a cycle queued by ``submit_cycle``: node ``node``'s value
-        per checkpoint, in commit order; ``values`` holds every node's."""
-        self.values = self._engine.wait(ticket).reshape(-1, self.n_nodes, 32)
-        return [v.tobytes() for v in self.values[:, self.node]]
-
-    def close(self) -> None:
-        self.streams.close()
+    _cycle = cycle_programme
 
 
 class GpuHash:

@@ -2,7 +2,9 @@
 // (mirbft_amd/csrc/mirsha_host.cpp, compiled here with g++: no HIP, no GPU):
 // the segments a commit submission of the ring sends to the device, against a
 // restatement built from the ops directly, with guard entries behind every
-// output, the segment count's formula, and the rejected programmes.  Prints
+// output, the segment count's formula, the rejected programmes, and a
+// differential check of both commit plans on small random programmes; and
+// mirsha::host::seg_straddle against its definition.  Prints
 // "commit seg unit ok"; exit 1 with a message at the first mismatch.
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "mirsha.h"
+#include "mirsha_host.h"
 
 static int fails = 0;
 #define EXPECT(cond, ...)                                        \
@@ -110,6 +113,161 @@ static void reject(const std::vector<uint32_t>& oc, const std::vector<uint32_t>&
            "%s: wrote past its outputs", what);
 }
 
+// ---- Differential check of mirsha_commit_plan and mirsha_commit_seg_plan: every
+// array (guards included: nothing is written before every op has passed),
+// every count, the code and the bad op, against a plain restatement -- the
+// argument checks in their order, a per-chain std::vector append in op order,
+// then a cut.
+struct Out {
+    int rc = 0;
+    uint32_t ns = kGuard, na = kGuard, ne = kGuard, nv = kGuard, bad = kGuard;
+    std::vector<uint32_t> act, efirst, seg_chain, sfirst, flags, ent;
+    explicit Out(uint32_t cap)
+        : act(cap + 2, kGuard), efirst(cap + 2, kGuard), seg_chain(cap + 2, kGuard), sfirst(cap + 2, kGuard),
+          flags(cap + 2, kGuard), ent(cap + 2, kGuard) {}
+    bool operator==(const Out& o) const {
+        return rc == o.rc && ns == o.ns && na == o.na && ne == o.ne && nv == o.nv && bad == o.bad && act == o.act &&
+               efirst == o.efirst && seg_chain == o.seg_chain && sfirst == o.sfirst && flags == o.flags && ent == o.ent;
+    }
+};
+
+static Out model(bool seg, const uint32_t* oc, const uint32_t* od, uint32_t n, uint32_t n_chains, uint32_t n_digests,
+                 bool outputs, uint32_t cap) {
+    Out w(cap);
+    w.bad = UINT32_MAX;
+    w.na = w.ne = w.nv = 0;
+    if (seg) w.ns = 0;
+    std::vector<uint32_t>& first = seg ? w.sfirst : w.efirst;
+    w.rc = MIRSHA_EINVAL;
+    if (n > kFlag || n_digests > kFlag) {
+        w.rc = MIRSHA_ERANGE;
+        return w;
+    }
+    if (n == 0) {
+        w.rc = MIRSHA_OK;
+        if (outputs) first[0] = 0;
+        return w;
+    }
+    if (!oc || !od) return w;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool marker = od[i] == MIRSHA_NULL_INDEX || od[i] == MIRSHA_COMMIT_CHECKPOINT;
+        if (oc[i] >= n_chains || (!marker && od[i] >= n_digests)) {
+            w.bad = i;
+            return w;
+        }
+    }
+    if (!outputs) return w;
+    std::vector<std::vector<uint32_t>> per(n_chains);
+    for (uint32_t i = 0; i < n; i++)
+        if (od[i] != MIRSHA_NULL_INDEX) per[oc[i]].push_back(od[i] == MIRSHA_COMMIT_CHECKPOINT ? (kFlag | w.nv++) : od[i]);
+    w.rc = MIRSHA_OK;
+    first[0] = 0;
+    for (uint32_t c = 0; c < n_chains; c++) {
+        const uint32_t e0 = w.ne;
+        for (size_t k = 0; k < per[c].size(); k++) {
+            w.ent[w.ne++] = per[c][k];
+            const bool last = k + 1 == per[c].size();
+            if (!seg || !((per[c][k] & kFlag) || last)) continue;
+            w.seg_chain[w.ns] = c;
+            // FIRST: no cut of this chain yet, so the segment begins at the chain's first entry
+            w.flags[w.ns] = (w.sfirst[w.ns] == e0 ? MIRSHA_COMMIT_SEG_FIRST : 0u) | (last ? MIRSHA_COMMIT_SEG_LAST : 0u);
+            w.sfirst[++w.ns] = w.ne;
+        }
+        if (per[c].empty()) continue;
+        if (!seg) {
+            w.act[w.na] = c;
+            w.efirst[w.na + 1] = w.ne;
+        }
+        w.na++;
+    }
+    return w;
+}
+
+static void differ(const uint32_t* oc, const uint32_t* od, uint32_t n, uint32_t n_chains, uint32_t n_digests,
+                   bool outputs, uint32_t cap, const char* what) {
+    for (int seg = 0; seg < 2; seg++) {
+        Out g(cap);
+        auto p = [&](std::vector<uint32_t>& v) { return outputs ? v.data() : nullptr; };
+        g.rc = seg ? mirsha_commit_seg_plan(oc, od, n, n_chains, n_digests, p(g.seg_chain), p(g.sfirst), p(g.flags),
+                                            p(g.ent), &g.ns, &g.na, &g.ne, &g.nv, &g.bad)
+                   : mirsha_commit_plan(oc, od, n, n_chains, n_digests, p(g.act), p(g.efirst), p(g.ent), &g.na, &g.ne,
+                                        &g.nv, &g.bad);
+        const Out w = model(seg != 0, oc, od, n, n_chains, n_digests, outputs, cap);
+        EXPECT(g == w, "%s (%s plan, %u ops): rc %d/%d bad %u/%u counts %u %u %u %u / %u %u %u %u", what,
+               seg ? "seg" : "commit", n, g.rc, w.rc, g.bad, w.bad, g.ns, g.na, g.ne, g.nv, w.ns, w.na, w.ne, w.nv);
+    }
+}
+
+static void differential() {
+    const uint32_t CP = MIRSHA_COMMIT_CHECKPOINT, NUL = MIRSHA_NULL_INDEX;
+    std::mt19937_64 rng(21);
+    for (int round = 0; round < 4000; round++) {
+        const uint32_t n_chains = 1 + (uint32_t)(rng() % 5), n_digests = (uint32_t)(rng() % 9);
+        const uint32_t n = (uint32_t)(rng() % 41);
+        std::vector<uint32_t> oc(n), od(n);
+        for (uint32_t i = 0; i < n; i++) {
+            oc[i] = (uint32_t)(rng() % n_chains);
+            const uint32_t k = (uint32_t)(rng() % 8);
+            od[i] = k == 0 ? NUL : (k < 3 || n_digests == 0) ? CP : (uint32_t)(rng() % n_digests);
+        }
+        const uint32_t cls = (uint32_t)(rng() % 12), at = n ? (uint32_t)(rng() % n) : 0u;
+        const uint32_t *pc = oc.data(), *pd = od.data();
+        bool outputs = true;
+        uint32_t nd = n_digests;
+        const char* what = "differential: a valid programme";
+        if (n && cls == 6) oc[at] = n_chains + (uint32_t)(rng() % 3), what = "differential: a bad chain";
+        if (n && cls == 7) od[at] = n_digests + (uint32_t)(rng() % 3), what = "differential: a bad digest index";
+        if (cls == 8) (rng() & 1 ? pc : pd) = nullptr, what = "differential: a NULL op array";
+        if (cls == 9) outputs = false, what = "differential: NULL outputs";
+        if (cls == 10) {  // with a bad op: the inner plan's code and bad op come first
+            outputs = false, what = "differential: NULL outputs and a bad op";
+            if (n) (rng() & 1 ? oc[at] = n_chains : od[at] = CP - 1u);
+        }
+        if (cls == 11 && round % 8 == 0) nd = kFlag + 1u, what = "differential: too many digests";
+        differ(pc, pd, n, n_chains, nd, outputs, n, what);
+    }
+    const uint32_t one[1] = {0};
+    differ(one, one, kFlag + 1u, 4, 3, true, 0, "differential: too many ops");  // refused before an array is read
+    differ(one, one, kFlag + 1u, 4, 3, false, 0, "differential: too many ops, NULL outputs");
+}
+
+// ---- mirsha::host::seg_straddle over the flags of owners with the given segment
+// counts, against the definition: a LAST lane whose wave index differs from
+// its owner's FIRST lane's.
+static void straddle(const std::vector<uint32_t>& seg_counts, bool want, const char* what) {
+    std::vector<uint32_t> flags;
+    for (uint32_t k : seg_counts)
+        for (uint32_t j = 0; j < k; j++)
+            flags.push_back((j == 0 ? MIRSHA_COMMIT_SEG_FIRST : 0u) | (j + 1 == k ? MIRSHA_COMMIT_SEG_LAST : 0u));
+    bool def = false;
+    for (size_t s = 0, first = 0; s < flags.size(); s++) {
+        if (flags[s] & MIRSHA_COMMIT_SEG_FIRST) first = s;
+        if ((flags[s] & MIRSHA_COMMIT_SEG_LAST) && s / 64 != first / 64) def = true;
+    }
+    EXPECT(def == want, "%s: the definition says %d", what, (int)def);
+    EXPECT(mirsha::host::seg_straddle(flags.data(), (uint32_t)flags.size(), 64) == want, "%s: not %d", what, (int)want);
+}
+
+static void straddles() {
+    EXPECT(!mirsha::host::seg_straddle(nullptr, 0, 64), "no segments");
+    straddle({1}, false, "one segment");
+    straddle({64}, false, "one chain over exactly one wave");
+    straddle({65}, true, "one chain over 65 lanes");
+    straddle(std::vector<uint32_t>(64, 1), false, "64 chains of one segment");
+    straddle(std::vector<uint32_t>(65, 1), false, "65 chains of one segment");
+    std::vector<uint32_t> lead(63, 1);  // 63 one-segment chains: the next chain's FIRST is lane 63
+    auto after63 = [&](uint32_t k) {
+        std::vector<uint32_t> v = lead;
+        v.push_back(k);
+        return v;
+    };
+    straddle(after63(1), false, "FIRST and LAST at lane 63");
+    straddle(after63(2), true, "FIRST at lane 63, LAST at lane 64");
+    straddle(after63(66), true, "FIRST at lane 63, LAST at lane 128");
+    straddle({60, 10}, true, "only the second chain straddles");
+    straddle({64, 1}, false, "a single FIRST | LAST segment at lane 64");
+}
+
 int main() {
     const uint32_t CP = MIRSHA_COMMIT_CHECKPOINT, NUL = MIRSHA_NULL_INDEX;
     check({}, {}, 4, 9, "empty");
@@ -173,6 +331,8 @@ int main() {
         EXPECT(mirsha_commit_seg_plan(nullptr, nullptr, 0, 4, 3, nullptr, nullptr, nullptr, nullptr, &cnt, &cnt, &cnt,
                                       &cnt, nullptr) == MIRSHA_OK && cnt == 0, "n_ops = 0 with NULL arrays");
     }
+    differential();
+    straddles();
     if (fails) return 1;
     printf("commit seg unit ok\n");
     return 0;

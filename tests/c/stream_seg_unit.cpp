@@ -3,8 +3,11 @@
 // the segments a stream submission of the ring sends to the device, against a
 // restatement built from the ops directly, with guard entries behind every
 // output, the entry arrays against mirsha_stream_plan's own, the segment
-// count's formula, and the rejected programmes.  Prints "stream seg unit ok";
-// exit 1 with a message at the first mismatch.
+// count's formula, the rejected programmes, and a differential check of both
+// stream plans on small random programmes; and mirsha::host::seg_straddle
+// against its definition.  Prints "stream seg unit ok"; exit 1 with a message
+// at the first mismatch.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -12,6 +15,7 @@
 #include <vector>
 
 #include "mirsha.h"
+#include "mirsha_host.h"
 
 static int fails = 0;
 #define EXPECT(cond, ...)                                        \
@@ -154,6 +158,225 @@ static void reject(const std::vector<Op>& ops, uint32_t n_streams, uint64_t aren
     EXPECT(rc2 == rc && bad2 == bad, "%s: mirsha_stream_plan says rc %d bad %u", what, rc2, bad2);
 }
 
+// ---- Differential check of mirsha_stream_plan and mirsha_stream_seg_plan: every
+// array (guards included: nothing is written before every op has passed),
+// every count, the code and the bad op, against a plain restatement -- the
+// argument checks in their order, a per-stream std::vector append in op
+// order, then a cut; with `pack`, every distinct range once in entry order.
+struct Out {
+    int rc = 0;
+    uint32_t ns = kGuard, na = kGuard, ne = kGuard, nv = kGuard, bad = kGuard;
+    uint64_t nb = kGuard64;
+    std::vector<uint32_t> act, efirst, seg_stream, sfirst, flags, kind, len;
+    std::vector<uint64_t> off;
+    explicit Out(uint32_t cap)
+        : act(cap + 2, kGuard), efirst(cap + 2, kGuard), seg_stream(cap + 2, kGuard), sfirst(cap + 2, kGuard),
+          flags(cap + 2, kGuard), kind(cap + 2, kGuard), len(cap + 2, kGuard), off(cap + 2, kGuard64) {}
+    bool operator==(const Out& o) const {
+        return rc == o.rc && ns == o.ns && na == o.na && ne == o.ne && nv == o.nv && bad == o.bad && nb == o.nb &&
+               act == o.act && efirst == o.efirst && seg_stream == o.seg_stream && sfirst == o.sfirst &&
+               flags == o.flags && kind == o.kind && len == o.len && off == o.off;
+    }
+};
+
+struct OpArrays {  // any of them may be NULL
+    const uint32_t *s, *k;
+    const uint64_t* o;
+    const uint32_t* l;
+};
+
+static Out model(bool seg, const OpArrays& a, uint32_t n, uint32_t n_streams, uint64_t arena_len, int pack,
+                 bool outputs, uint32_t cap) {
+    Out w(cap);
+    w.bad = UINT32_MAX;
+    w.na = w.ne = w.nv = 0;
+    w.nb = 0;
+    if (seg) w.ns = 0;
+    std::vector<uint32_t>& first = seg ? w.sfirst : w.efirst;
+    w.rc = MIRSHA_EINVAL;
+    if (n > MIRSHA_STREAM_MAX_OPS) {
+        w.rc = MIRSHA_ERANGE;
+        return w;
+    }
+    if (n == 0) {
+        w.rc = MIRSHA_OK;
+        if (outputs) first[0] = 0;
+        return w;
+    }
+    if (!a.s || !a.k) return w;
+    bool writes = false;
+    for (uint32_t i = 0; i < n; i++) writes |= a.k[i] == W;
+    if (writes && (!a.o || !a.l)) return w;
+    for (uint32_t i = 0; i < n; i++) {
+        bool ok = a.s[i] < n_streams && a.k[i] <= R;
+        if (ok && a.k[i] == W) ok = a.o[i] <= arena_len && a.l[i] <= arena_len - a.o[i];
+        if (!ok) {
+            w.bad = i;
+            return w;
+        }
+    }
+    if (!outputs) return w;
+    struct Ent {
+        uint32_t kind, len;
+        uint64_t off;
+    };
+    std::vector<std::vector<Ent>> per(n_streams);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t k = a.k[i];
+        if (k == W && a.l[i] == 0) continue;
+        const bool sum = k == S || k == SR;
+        per[a.s[i]].push_back({k | (sum ? w.nv++ << 2 : 0u), k == W ? a.l[i] : 0u, k == W ? a.o[i] : 0u});
+    }
+    w.rc = MIRSHA_OK;
+    first[0] = 0;
+    std::map<std::pair<uint64_t, uint32_t>, uint64_t> packed;  // range -> where its bytes lie
+    for (uint32_t s = 0; s < n_streams; s++) {
+        const uint32_t e0 = w.ne;
+        for (size_t k = 0; k < per[s].size(); k++) {
+            const Ent& e = per[s][k];
+            w.kind[w.ne] = e.kind;
+            w.len[w.ne] = e.len;
+            w.off[w.ne] = e.off;
+            if (!pack) {
+                w.nb += e.len;
+            } else if (e.len) {
+                const auto it = packed.emplace(std::make_pair(e.off, e.len), w.nb);
+                w.off[w.ne] = it.first->second;
+                if (it.second) w.nb += e.len;
+            }
+            w.ne++;
+            const bool last = k + 1 == per[s].size();
+            if (!seg || !(cuts(e.kind & 3u) || last)) continue;
+            w.seg_stream[w.ns] = s;
+            // FIRST: no cut of this stream yet, so the segment begins at the stream's first entry
+            w.flags[w.ns] = (w.sfirst[w.ns] == e0 ? MIRSHA_STREAM_SEG_FIRST : 0u) | (last ? MIRSHA_STREAM_SEG_LAST : 0u);
+            w.sfirst[++w.ns] = w.ne;
+        }
+        if (per[s].empty()) continue;
+        if (!seg) {
+            w.act[w.na] = s;
+            w.efirst[w.na + 1] = w.ne;
+        }
+        w.na++;
+    }
+    return w;
+}
+
+static void differ(const OpArrays& a, uint32_t n, uint32_t n_streams, uint64_t arena_len, bool outputs, uint32_t cap,
+                   const char* what) {
+    for (int seg = 0; seg < 2; seg++)
+        for (int pack = 0; pack < 2; pack++) {
+            Out g(cap);
+            auto p = [&](std::vector<uint32_t>& v) { return outputs ? v.data() : nullptr; };
+            uint64_t* po = outputs ? g.off.data() : nullptr;
+            g.rc = seg ? mirsha_stream_seg_plan(a.s, a.k, a.o, a.l, n, n_streams, arena_len, pack, p(g.seg_stream),
+                                                p(g.sfirst), p(g.flags), p(g.kind), po, p(g.len), &g.ns, &g.na, &g.ne,
+                                                &g.nv, &g.nb, &g.bad)
+                       : mirsha_stream_plan(a.s, a.k, a.o, a.l, n, n_streams, arena_len, pack, p(g.act), p(g.efirst),
+                                            p(g.kind), po, p(g.len), &g.na, &g.ne, &g.nv, &g.nb, &g.bad);
+            const Out w = model(seg != 0, a, n, n_streams, arena_len, pack, outputs, cap);
+            EXPECT(g == w, "%s (%s plan, pack %d, %u ops): rc %d/%d bad %u/%u counts %u %u %u %u %llu / %u %u %u %u %llu",
+                   what, seg ? "seg" : "stream", pack, n, g.rc, w.rc, g.bad, w.bad, g.ns, g.na, g.ne, g.nv,
+                   (unsigned long long)g.nb, w.ns, w.na, w.ne, w.nv, (unsigned long long)w.nb);
+        }
+}
+
+static void differential() {
+    std::mt19937_64 rng(22);
+    for (int round = 0; round < 4000; round++) {
+        const uint32_t n_streams = 1 + (uint32_t)(rng() % 5);
+        const uint64_t arena_len = rng() % 201;
+        const uint32_t n = (uint32_t)(rng() % 41);
+        std::vector<Op> ops(n);
+        for (uint32_t i = 0; i < n; i++) {
+            Op& o = ops[i];
+            o.stream = (uint32_t)(rng() % n_streams);
+            o.kind = (uint32_t)(rng() % 6);
+            if (o.kind == W || o.kind > R) {
+                o.kind = W;
+                if (i && ops[i - 1].kind == W && rng() % 3 == 0) {  // the same range again
+                    o.off = ops[i - 1].off, o.len = ops[i - 1].len;
+                } else {
+                    o.off = rng() % (arena_len + 1);
+                    o.len = rng() % 5 == 0 ? 0u : (uint32_t)(rng() % (arena_len - o.off + 1));
+                }
+            } else {
+                o.off = rng();  // ignored
+                o.len = (uint32_t)rng();
+            }
+        }
+        const uint32_t cls = (uint32_t)(rng() % 13), at = n ? (uint32_t)(rng() % n) : 0u;
+        bool outputs = true;
+        const char* what = "differential: a valid programme";
+        if (n && cls == 6) ops[at].stream = n_streams + (uint32_t)(rng() % 3), what = "differential: a bad stream";
+        if (n && cls == 7) ops[at].kind = R + 1u + (uint32_t)(rng() % 3), what = "differential: a bad kind";
+        if (n && cls == 8) {
+            what = "differential: a write out of range";
+            ops[at].kind = W;
+            ops[at].off = rng() % (arena_len + 3);
+            ops[at].len = (uint32_t)(arena_len - std::min(arena_len, ops[at].off)) + 1u;
+        }
+        if (cls == 10) outputs = false, what = "differential: NULL outputs";
+        if (cls == 11) {  // with a bad op: the inner plan's code and bad op come first
+            outputs = false, what = "differential: NULL outputs and a bad op";
+            if (n) ops[at].stream = n_streams;
+        }
+        const Arrays a(ops);
+        OpArrays p = {a.s.data(), a.k.data(), a.o.data(), a.l.data()};
+        if (cls == 9) {
+            what = "differential: a NULL op array";
+            const uint32_t which = (uint32_t)(rng() % 4);
+            if (which == 0) p.s = nullptr;
+            if (which == 1) p.k = nullptr;
+            if (which == 2) p.o = nullptr;  // refused only when an op writes
+            if (which == 3) p.l = nullptr;
+        }
+        differ(p, n, n_streams, arena_len, outputs, n, what);
+    }
+    const uint32_t one[1] = {0};
+    const uint64_t one64[1] = {0};
+    const OpArrays p = {one, one, one64, one};
+    differ(p, MIRSHA_STREAM_MAX_OPS + 1u, 4, 3, true, 0, "differential: too many ops");  // refused before an array is read
+    differ(p, MIRSHA_STREAM_MAX_OPS + 1u, 4, 3, false, 0, "differential: too many ops, NULL outputs");
+}
+
+// ---- mirsha::host::seg_straddle over the flags of owners with the given segment
+// counts, against the definition: a LAST lane whose wave index differs from
+// its owner's FIRST lane's.
+static void straddle(const std::vector<uint32_t>& seg_counts, bool want, const char* what) {
+    std::vector<uint32_t> flags;
+    for (uint32_t k : seg_counts)
+        for (uint32_t j = 0; j < k; j++)
+            flags.push_back((j == 0 ? MIRSHA_STREAM_SEG_FIRST : 0u) | (j + 1 == k ? MIRSHA_STREAM_SEG_LAST : 0u));
+    bool def = false;
+    for (size_t s = 0, first = 0; s < flags.size(); s++) {
+        if (flags[s] & MIRSHA_STREAM_SEG_FIRST) first = s;
+        if ((flags[s] & MIRSHA_STREAM_SEG_LAST) && s / 64 != first / 64) def = true;
+    }
+    EXPECT(def == want, "%s: the definition says %d", what, (int)def);
+    EXPECT(mirsha::host::seg_straddle(flags.data(), (uint32_t)flags.size(), 64) == want, "%s: not %d", what, (int)want);
+}
+
+static void straddles() {
+    EXPECT(!mirsha::host::seg_straddle(nullptr, 0, 64), "no segments");
+    straddle({1}, false, "one segment");
+    straddle({64}, false, "one stream over exactly one wave");
+    straddle({65}, true, "one stream over 65 lanes");
+    straddle(std::vector<uint32_t>(64, 1), false, "64 streams of one segment");
+    straddle(std::vector<uint32_t>(65, 1), false, "65 streams of one segment");
+    std::vector<uint32_t> lead(63, 1);  // 63 one-segment streams: the next stream's FIRST is lane 63
+    auto after63 = [&](uint32_t k) {
+        std::vector<uint32_t> v = lead;
+        v.push_back(k);
+        return v;
+    };
+    straddle(after63(1), false, "FIRST and LAST at lane 63");
+    straddle(after63(2), true, "FIRST at lane 63, LAST at lane 64");
+    straddle(after63(66), true, "FIRST at lane 63, LAST at lane 128");
+    straddle({60, 10}, true, "only the second stream straddles");
+    straddle({64, 1}, false, "a single FIRST | LAST segment at lane 64");
+}
+
 int main() {
     check({}, 4, 9, "empty");
     check({{0, W, 0, 0}, {3, W, 5, 0}}, 4, 9, "zero-length writes only");
@@ -233,6 +456,8 @@ int main() {
                                       nullptr, nullptr, nullptr, &cnt, &cnt, &cnt, &cnt, &nb, nullptr) == MIRSHA_OK &&
                    cnt == 0, "n_ops = 0 with NULL arrays");
     }
+    differential();
+    straddles();
     if (fails) return 1;
     printf("stream seg unit ok\n");
     return 0;
