@@ -87,10 +87,8 @@ void* mirsha_ctx_stream(mirsha_ctx* ctx);
  * 10 = the CU-block kernel at any size (groups beyond 4 per SIMD run in
  *     later workgroups, one CU at a time).
  * All of these are bit-exact.  Anything else is EINVAL: 2, 3, 7, 8 (round-1
- * A/B forms) are retired, and 11-15 (retired and diagnostic forms of the
- * CU-block kernel, one of which skips its loads) exist only in the tools A/B
- * build (tools/ab_build.sh lib), never in this library, whatever the
- * environment says. */
+ * A/B forms) and 11-15 (earlier and diagnostic forms of the CU-block kernel)
+ * are retired: no build holds them, whatever the environment says. */
 int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
 
 /* Per-kernel device-time accounting with HIP events bound to each timed

@@ -267,7 +267,7 @@ def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    # MIRSHA_AB_LIB: an A/B build of the same sources (tools/ab_build.sh) for
+    # MIRSHA_AB_LIB: an A/B build of the same sources (tools/yield_sweep.sh) for
     # same-box timing comparisons; never set by tests, smoke() or the driver.
     path = os.environ.get("MIRSHA_AB_LIB") or LIB_PATH
     if not os.path.exists(path):

@@ -21,34 +21,18 @@ enum : int {
     kVariantLdsOnly = 5,
     kVariantPair = 6,
     kVariantCu = 10,      // CU-block form (one workgroup per CU, LDS-DMA loads one block ahead; <= 4 tiles per SIMD)
-    // Forms of the CU-block kernel compiled ONLY into the tools A/B library
-    // (tools/ab_build.sh lib, -DMIRSHA_AB_FORMS; never the product):
-    kVariantCuNoYield = 11,  // register-prefetching block loop, no-yield rounds
-    kVariantCuPrefetch = 12, // register-prefetching block loop (round 3's product form)
-    kVariantCuDmaPipe = 13,  // LDS-DMA, the next block's words read back mid-block
-    kVariantCuDiagNoLoads = 14,  // diagnostic: without its block loads (its digests are NOT valid)
-    kVariantCuDiagNoPrio = 15,   // diagnostic: without its per-block issue priorities
+    // (11-15, round 3 / 4 forms of the CU-block kernel, are retired: DESIGN.md §7)
 };
 const char* ab_getenv(const char* name);
-inline bool variant_is_ab_form(int v) {
-#ifdef MIRSHA_AB_FORMS
-    return v >= kVariantCuNoYield && v <= kVariantCuDiagNoPrio;
-#else
-    (void)v;
-    return false;  // the product library accepts bit-exact forms only
-#endif
-}
 inline bool variant_valid(int v) {
     return v == kVariantLds || v == kVariantDirect || v == kVariantLowOcc || v == kVariantLdsOnly || v == kVariantPair ||
-           v == kVariantCu || variant_is_ab_form(v);
+           v == kVariantCu;
 }
 constexpr uint32_t kCuMaxWavesPerSimd = 4;
 uint32_t cu_count();
 // Schedule A/B and diagnostic knobs are read from the environment only when
-// MIRSHA_AB=1 is set too (never in production).  Every knob the product
-// library reads keeps the digests bit-exact (tests/test_gpu_parity.py runs
-// them); the one form that does not (variant 14) exists only in the tools
-// A/B library.
+// MIRSHA_AB=1 is set too (never in production).  Every knob the library
+// reads keeps the digests bit-exact (tests/test_gpu_parity.py runs them).
 constexpr uint32_t kLowOccTiles = 1024;   // 256 CUs x 4 SIMDs
 // Small launches take a latency form: at most pair_max_groups() 64-message
 // groups (default kPairMaxGroups: <= 2 pairs per CU, every wave alone on a

@@ -312,105 +312,71 @@ __device__ __forceinline__ void balance_done() {
     __hip_atomic_store(g_bal_prog + bal_word(), kBalDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// Software-pipelined block loop of a tile (kPf: launches of at most 4 waves
-// per SIMD, which leave a wave 128 VGPRs), for tiles whose messages are all
-// 4-byte aligned and whose loads all stay inside the arena.  Block b+1's
-// words are staged WHILE block b's rounds run, between the round statements
-// (compress_asm_hooked): after rounds 0-7 its raw chunks (loaded one block
-// earlier) are byte-swapped and written to the wave's LDS tile and block b+2's
-// chunks are loaded; after rounds 16-23 the transposed words are read back.
-// So the transpose's LDS round trip and the loads hide behind this wave's own
-// rounds: with 4 waves per SIMD started together (config 3) the waves reach
-// their staging at the same time and the one-at-a-time form left the SIMD
-// short of issuable waves there (643 us per config-3 launch, profiles/r03b).
-template <bool kNoYield>
-__device__ __forceinline__ void hash_tile_pipelined(__amdgpu_buffer_rsrc_t rsrc, const uint32_t vo[4],
-                                                    const uint32_t sel[4], uint32_t L, uint32_t min_l, bool uni,
-                                                    bool tail_ok, const TailWords& tw, uint32_t wave_nb,
-                                                    uint32_t loop_nb, uint32_t nb, uint32_t lane, uint4* my,
-                                                    uint32_t st[8]) {
-    const uint32_t q = lane & 3u;
-    uint32_t nx[4][4];  // raw chunks of the next block to stage
-    auto load_raw = [&](uint32_t blk) {
+// Cross-lane hand-off through LDS inside one wave: LDS ops of a wave execute
+// in order; the fences only stop the compiler from reordering.
+__device__ __forceinline__ void wave_lds_handoff() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// This lane's message, 16 words, out of a swizzled tile: four ds_read_b128.
+__device__ __forceinline__ void tile_read_words(const uint4* tile, uint32_t lane, uint32_t w[16]) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo[j], 64u * blk, 0);
-            nx[j][0] = v[0]; nx[j][1] = v[1]; nx[j][2] = v[2]; nx[j][3] = v[3];
-        }
-    };
-    // Words of block blk (raw chunks in nx) into the LDS tile; mixed tiles pad
-    // per chunk here, uniform tiles after the read (pad_block_uniform).
-    auto write_tile = [&](uint32_t blk) {
-        const uint32_t soff = 64u * blk;
-        const bool pad = soff + 64u > min_l;  // wave-uniform
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            uint32_t wq[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) wq[k] = be_word(k < 3 ? nx[j][k + 1] : 0u, nx[j][k], sel[j]);
-            if (pad && !uni) {
-                const uint32_t Lm = (uint32_t)__shfl((int)L, 16 * j + (int)(lane >> 2), 64);
-                pad_words(soff + 16u * q, Lm, blk + 1u == blocks_for_len(Lm), q, wq);
-            }
-            my[lds_slot(16u * j + (lane >> 2), q)] = make_uint4(wq[0], wq[1], wq[2], wq[3]);
-        }
-        // LDS ops of a wave execute in order; the fences only keep the compiler
-        // from moving the reads above the writes.
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    auto read_tile = [&](uint32_t w[16]) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint4 x = my[lds_slot(lane, (uint32_t)k)];
-            w[4 * k + 0] = x.x; w[4 * k + 1] = x.y; w[4 * k + 2] = x.z; w[4 * k + 3] = x.w;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    auto pad_uniform = [&](uint32_t blk, uint32_t w[16]) {
-        if (64u * blk + 64u > min_l && uni) {  // wave-uniform
-            uint32_t wnb;  // opaque copy: no loop peeling to fold the test (see hash_tile)
-            asm volatile("s_mov_b32 %0, %1" : "=s"(wnb) : "s"(wave_nb));
-            pad_block_uniform(w, 64u * blk, min_l, wnb - blk == 1u);
-        }
-    };
-    uint32_t w[16];
-    load_raw(0u);
-    write_tile(0u);
-    if (1u < wave_nb) load_raw(1u);
-    read_tile(w);
-    for (uint32_t blk = 0; blk < loop_nb; blk++) {
-        pad_uniform(blk, w);
-        const bool next = blk + 1u < wave_nb;  // wave-uniform
-        uint32_t wn[16];
-        progress_prio(blk);
-        compress_asm_hooked<kNoYield>(st, w, blk < nb, [&](int k) {
-            if (k == 0 && next) {
-                write_tile(blk + 1u);
-                if (blk + 2u < wave_nb) load_raw(blk + 2u);
-            } else if (k == 2 && next) {
-                read_tile(wn);
-            }
-        });
-#pragma unroll
-        for (int i = 0; i < 16; i++) w[i] = wn[i];
+    for (int k = 0; k < 4; k++) {
+        const uint4 x = tile[lds_slot(lane, (uint32_t)k)];
+        w[4 * k + 0] = x.x; w[4 * k + 1] = x.y; w[4 * k + 2] = x.z; w[4 * k + 3] = x.w;
     }
-    if (tail_ok) {  // final block (<= 16 message bytes), staged during the loop's last block
-        const uint32_t blk = wave_nb - 1u;
-        pad_block_uniform<4>(w, 64u * blk, min_l, false);
+}
+
+// Whether blk is the last of a tile's wave_nb blocks, with the block count
+// through an opaque s_mov: hipcc otherwise peels the block loop's last
+// iteration to fold the test, a third copy of the rounds.  An s_mov, not the
+// s_sub_u32 of before: SALU arithmetic writes SCC behind the compiler's back,
+// and a padding mask's s_cselect read the clobbered SCC -- a wrong 0x80
+// marker at length 60, tests/test_gpu_parity.py uniform tiles.
+__device__ __forceinline__ bool last_block_opaque(uint32_t wave_nb, uint32_t blk) {
+    uint32_t wnb;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(wnb) : "s"(wave_nb));
+    return wnb - blk == 1u;
+}
+
+// A tile's digest: kFused with sc1, for list waves on other CUs; kBuf through
+// 32-bit buffer offsets (launch_msgs sends n >= 2^27 to the wide form): the
+// message index stays one VGPR across the block loop instead of a 64-bit
+// address pair (the tail form spilled it).
+template <bool kFused, bool kBuf>
+__device__ __forceinline__ void tile_store(uint8_t* out, uint32_t n, uint32_t msg, const uint32_t st[8]) {
+    if constexpr (kFused || kBuf) {
+        const __amdgpu_buffer_rsrc_t ors =
+            __builtin_amdgcn_make_buffer_rsrc((void*)out, (short)0, (int)(32u * n), 0x00020000);
+        if constexpr (kFused)
+            store_digest_sc1(ors, msg, st);
+        else
+            store_digest_buf(ors, msg, st);
+    } else {
+        store_digest(out, msg, st);
+    }
+}
+
+template <bool kFused>
+__device__ __forceinline__ void block_prio(uint32_t fprio, uint32_t blk) {
+    if constexpr (kFused) {
+        if (fprio == kPrioBalance)
+            balance_prio(blk);
+        else if (fprio == kPrioProgress)
+            progress_prio(blk);
+        else
+            fixed_prio(fprio);
+    } else {
         progress_prio(blk);
-        if (blk < nb) compress_asm_tail(st, w, tw);
     }
 }
 
 // kFused (sha256_fused_paced_kernel's tile waves): blocks at the fixed
 // priority fprio, digests stored with sc1 for list waves on other CUs.
-// kPf (launches of at most 4 waves per SIMD, which leave 128 VGPRs per wave):
-// the next block's chunks are staged while this block's rounds run
-// (hash_tile_pipelined).
+// kDma (the CU-block kernel; kFused implies it): aligned in-range tiles load
+// their blocks by LDS-DMA, one block ahead of the rounds.
 // Block range (the fused launch's split tiles, LDS loader only): blocks
 // [b0, b1) of the tile, from the midstate in st (H0 when b0 == 0).  Returns
 // kTileDone when the range reached the tile's end (the digest is then
@@ -418,11 +384,7 @@ __device__ __forceinline__ void hash_tile_pipelined(__amdgpu_buffer_rsrc_t rsrc,
 // block b1 - 1).  (A range that starts at or past the tile's end is never
 // passed: the fused launch skips such split-tile segments itself.)
 constexpr uint32_t kTilePaused = 0, kTileDone = 1;
-// kDiag (diagnostic builds of the CU-block kernel only, variants 14 / 15,
-// MIRSHA_AB=1; digests are NOT valid under 1): 1 = no block loads (the
-// rounds run on the LDS tile's stale words), 2 = no per-block s_setprio.
-template <bool kLds, bool kWide, bool kFused = false, bool kPf = false, bool kNoYield = false, bool kDma = false,
-          bool kDmaPipe = false, int kDiag = 0>
+template <bool kLds, bool kWide, bool kFused = false, bool kDma = false>
 __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena, uint64_t arena_len,
                                           const uint64_t* __restrict__ off, const uint32_t* __restrict__ len,
                                           const uint32_t* __restrict__ order, uint32_t n, uint8_t* __restrict__ out,
@@ -430,20 +392,6 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
                                           uint32_t b0 = 0u, uint32_t b1 = 0xFFFFFFFFu, uint32_t* st_io = nullptr,
                                           uint32_t lone_sel = 0u, uint4* my2 = nullptr,
                                           unsigned long long* lone_tr = nullptr) {
-    auto block_prio = [&](uint32_t blk) {
-        if constexpr (kDiag == 2) {
-            return;
-        } else if constexpr (kFused) {
-            if (fprio == kPrioBalance)
-                balance_prio(blk);
-            else if (fprio == kPrioProgress)
-                progress_prio(blk);
-            else
-                fixed_prio(fprio);
-        } else {
-            progress_prio(blk);
-        }
-    };
     // Prologue at the highest issue priority, back to 0 at the first
     // compression: a fresh wave is the youngest on its SIMD and at the default
     // priority gets the VALU only when every older wave stalls, so its
@@ -574,43 +522,25 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
                 // Unconditional: a slot of a finished message is never read.
                 my[lds_slot(16u * j + (ln >> 2), qq)] = make_uint4(wq[0], wq[1], wq[2], wq[3]);
             }
-            // Cross-lane hand-off inside one wave: LDS ops of a wave execute
-            // in order; the fences only stop the compiler from reordering.
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint4 x = my[lds_slot(ln, (uint32_t)k)];
-                w[4 * k + 0] = x.x; w[4 * k + 1] = x.y; w[4 * k + 2] = x.z; w[4 * k + 3] = x.w;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_handoff();
+            tile_read_words(my, ln, w);
+            wave_lds_handoff();
         };
         // A uniform tile's tail-form final block runs after the loop, not as a
         // branch inside it: two round copies joined inside the loop made the
         // register allocator spill (64 VGPRs is the 8-wave budget).
         const uint32_t loop_nb = tail_ok ? wave_nb - 1u : wave_nb;
-        if constexpr (kPf && !kDma && !kDmaPipe) {
-            if (far && aligned && b0 == 0u && finished) {
-                hash_tile_pipelined<kNoYield>(rsrc, vo, sel, L, min_l, uni, tail_ok, tw, wave_nb, loop_nb, nb, lane, my,
-                                              st);
-                goto digest;
-            }
-        }
         const uint32_t loop_end = min(loop_nb, b1);
         // Fused launch, aligned in-range tiles: the block loop below with the
         // loads as LDS-DMA (buffer_load_dwordx4 ... lds), block b+1's issued as
         // soon as block b's words are read back, so they land while b's rounds
         // run.  The fused launch runs 4 waves per SIMD and fewer as its queues
         // end (the last queue runs its final stretch alone), where the
-        // register-staged loader's load latency was exposed every block; the
-        // register prefetch of hash_tile_pipelined does not fit its 128 VGPRs.
+        // register-staged loader's load latency was exposed every block.
         // Lane l of piece j fetches slot 64 j + l of the swizzled tile
         // (lds_slot's inverse), so the transposed read back is the loader's.
         bool dma = false;
-        if constexpr (kFused || kDma || kDmaPipe) dma = far && aligned;
+        if constexpr (kFused || kDma) dma = far && aligned;
         if (dma) {
             const uint32_t qd = (lane & 3u) ^ ((lane >> 4) & 3u);
             uint32_t vd[4];
@@ -624,7 +554,6 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
             const bool deep = kFused && my2 != nullptr;  // wave-uniform
             auto tile_of = [&](uint32_t blk) { return (deep && (blk & 1u)) ? my2 : my; };
             auto issue_dma = [&](uint32_t blk) {
-                if constexpr (kDiag == 1) return;
                 uint4* t = tile_of(blk);
 #pragma unroll
                 for (int j = 0; j < 4; j++)
@@ -637,64 +566,11 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
             const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b0);
             const uint32_t d1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)loop_end);
             const uint32_t dmin = (uint32_t)__builtin_amdgcn_readfirstlane((int)min_l);
-            // kDmaPipe (A/B): block b+1's words are read back from LDS in the
-            // middle of block b's rounds (after statement 2; the wait for the
-            // reads after statement 4, then block b+2's DMA), so neither the
-            // DMA's landing nor the LDS round trip sits between two blocks.
-            // 16 more live VGPRs (the next block's words): CU-block kernel only.
-            auto read_words = [&](uint32_t x[16]) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the block landed in LDS
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint4 v = my[lds_slot(lane, (uint32_t)k)];
-                    x[4 * k + 0] = v.x; x[4 * k + 1] = v.y; x[4 * k + 2] = v.z; x[4 * k + 3] = v.w;
-                }
-            };
-            auto finish_words = [&](uint32_t blk, uint32_t x[16]) {
-#pragma unroll
-                for (int k = 0; k < 16; k++) x[k] = __builtin_bswap32(x[k]);
-                if (64u * blk + 64u > dmin) {  // wave-uniform
-                    uint32_t wnb;  // (opaque copy, as below)
-                    asm volatile("s_mov_b32 %0, %1" : "=s"(wnb) : "s"(wave_nb));
-                    if (uni) {
-                        pad_block_uniform(x, 64u * blk, dmin, wnb - blk == 1u);
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; k++)
-                            pad_words(64u * blk + 16u * (uint32_t)k, L, blk + 1u == nb, (uint32_t)k, &x[4 * k]);
-                    }
-                }
-            };
-            if constexpr (kDmaPipe) {
-                if (d0 < d1) {
-                    uint32_t w[16];
-                    issue_dma(d0);
-                    read_words(w);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if (d0 + 1u < d1) issue_dma(d0 + 1u);
-                    for (uint32_t blk = d0; blk < d1; blk++) {
-                        finish_words(blk, w);
-                        block_prio(blk);
-                        const bool next = blk + 1u < d1, next2 = blk + 2u < d1;  // wave-uniform
-                        uint32_t wn[16];
-                        compress_asm_hooked(st, w, blk < nb, [&](int k) {
-                            if (k == 2 && next) {
-                                read_words(wn);
-                            } else if (k == 4 && next) {
-                                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // reads back: free the tile
-                                if (next2) issue_dma(blk + 2u);
-                            }
-                        });
-#pragma unroll
-                        for (int i = 0; i < 16; i++) w[i] = wn[i];
-                    }
-                }
-            }
-            if (!kDmaPipe && d0 < d1) {
+            if (d0 < d1) {
                 issue_dma(d0);
                 if (deep && d0 + 1u < d1) issue_dma(d0 + 1u);
             }
-            for (uint32_t blk = kDmaPipe ? d1 : d0; blk < d1; blk++) {
+            for (uint32_t blk = d0; blk < d1; blk++) {
                 const uint32_t soff = 64u * blk;
                 // block blk landed in LDS (deep: block blk + 1's 4 loads may stay in flight)
                 if (deep && blk + 1u < d1)
@@ -706,7 +582,7 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
                 // LDS ops, before which hipcc waits for every in-flight LDS-DMA
                 // (lds_load_nodma); here that wait is already paid (one block
                 // in flight; the deep staging is off in overlapped launches).
-                if constexpr (kFused) block_prio(blk);
+                if constexpr (kFused) block_prio<true>(fprio, blk);
                 uint32_t w[16];
                 const uint4* tb = tile_of(blk);
 #pragma unroll
@@ -720,17 +596,16 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
 #pragma unroll
                 for (int k = 0; k < 16; k++) w[k] = __builtin_bswap32(w[k]);
                 if (soff + 64u > dmin) {  // wave-uniform
-                    uint32_t wnb;  // (opaque copy, as below)
-                    asm volatile("s_mov_b32 %0, %1" : "=s"(wnb) : "s"(wave_nb));
+                    const bool last = last_block_opaque(wave_nb, blk);
                     if (uni) {
-                        pad_block_uniform(w, soff, dmin, wnb - blk == 1u);
+                        pad_block_uniform(w, soff, dmin, last);
                     } else {  // each lane pads its own message
 #pragma unroll
                         for (int k = 0; k < 4; k++)
                             pad_words(soff + 16u * (uint32_t)k, L, blk + 1u == nb, (uint32_t)k, &w[4 * k]);
                     }
                 }
-                if constexpr (!kFused) block_prio(blk);
+                if constexpr (!kFused) block_prio<false>(fprio, blk);
                 if constexpr (kFused) {
                     // the SIMD's only live wave: latency round form (g_simd_live;
                     // the count only falls, so once alone the wave stops reading it)
@@ -753,18 +628,9 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
             const uint32_t soff = 64u * blk;
             uint32_t w[16];
             stage(blk, w, lane, false);
-            if (soff + 64u > min_l && uni) {  // wave-uniform
-                // (the block count through an opaque s_mov: hipcc otherwise
-                // peels the loop's last iteration to fold the test, a third
-                // copy of the rounds.  An s_mov, not the s_sub_u32 of before:
-                // SALU arithmetic writes SCC behind the compiler's back, and a
-                // padding mask's s_cselect read the clobbered SCC -- a wrong
-                // 0x80 marker at length 60, tests/test_gpu_parity.py uniform tiles)
-                uint32_t wnb;
-                asm volatile("s_mov_b32 %0, %1" : "=s"(wnb) : "s"(wave_nb));
-                pad_block_uniform(w, soff, min_l, wnb - blk == 1u);
-            }
-            block_prio(blk);
+            if (soff + 64u > min_l && uni)  // wave-uniform
+                pad_block_uniform(w, soff, min_l, last_block_opaque(wave_nb, blk));
+            block_prio<kFused>(fprio, blk);
             if (blk < nb) compress_asm(st, w);
         }
         // Final block of a uniform tile holding at most 16 message bytes
@@ -782,7 +648,7 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
             asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
             stage(blk, w, ln, true);
             pad_block_uniform<4>(w, 64u * blk, min_l, false);
-            block_prio(blk);
+            block_prio<kFused>(fprio, blk);
             if (blk < nb) compress_asm_tail(st, w, tw);
         }
     } else if constexpr (kLds) {
@@ -809,18 +675,14 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
                 finish_chunk(rc[j], 64u * blk + 16u * q, Lj[j], blk + 1u == nbj[j], q, wq);
                 my[lds_slot(16u * j + (lane >> 2), q)] = make_uint4(wq[0], wq[1], wq[2], wq[3]);
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_handoff();
             uint32_t w[16];
 #pragma unroll
             for (int k = 0; k < 4; k++) {
                 const uint4 x = my[lds_slot(lane, (uint32_t)k)];
                 w[4 * k + 0] = x.x; w[4 * k + 1] = x.y; w[4 * k + 2] = x.z; w[4 * k + 3] = x.w;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_handoff();
             progress_prio(blk);
             if (blk < nb) compress_asm(st, w);
         }
@@ -838,28 +700,12 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
             if (active) compress_asm(st, w);
         }
     }
-digest:
     if (!finished) {  // a split tile's range: hand the midstate back
 #pragma unroll
         for (int i = 0; i < 8; i++) st_io[i] = st[i];
         return kTilePaused;
     }
-    if (valid) {
-        if constexpr (kFused) {
-            const __amdgpu_buffer_rsrc_t ors =
-                __builtin_amdgcn_make_buffer_rsrc((void*)out, (short)0, (int)(32u * n), 0x00020000);
-            store_digest_sc1(ors, msg, st);
-        } else if constexpr (kLds && !kWide) {
-            // 32-bit buffer offsets (launch_msgs sends n >= 2^27 to the wide
-            // form): the message index stays one VGPR across the block loop
-            // instead of a 64-bit address pair (the tail form spilled it).
-            const __amdgpu_buffer_rsrc_t ors =
-                __builtin_amdgcn_make_buffer_rsrc((void*)out, (short)0, (int)(32u * n), 0x00020000);
-            store_digest_buf(ors, msg, st);
-        } else {
-            store_digest(out, msg, st);
-        }
-    }
+    if (valid) tile_store<kFused, kLds && !kWide>(out, n, msg, st);
     return kTileDone;
 }
 
@@ -891,18 +737,13 @@ __global__ __launch_bounds__(64 * kMsgWaves, kWide ? 6 : kMsgOcc) void sha256_ms
 // SIMDs ran 5-6 tiles while others idled.  Here each CU gets ONE workgroup of
 // 4k waves (kCuLds of LDS holds it alone on its CU), which the CU deals to
 // its SIMDs in cyclic order: exactly k waves per SIMD.  Each wave's next
-// block lands in its LDS tile by DMA while this block's rounds run (kMode 0).
+// block lands in its LDS tile by DMA while this block's rounds run: block
+// b+1's loads are issued as LDS-DMA (buffer_load_dwordx4 ... lds) as soon as
+// block b's words are read back, the fused launch's loader (config 3
+// sequential plan, same box: 0.632-0.634 vs 0.648 ms for the
+// register-prefetching form, 1,424 vs 1,443 VALU per compression,
+// profiles/r04a, r04b).  DESIGN.md §7 records the retired forms of this kernel.
 constexpr uint32_t kCuLds = 96u * 1024u;
-// kMode: 0 = the product form: block b+1's loads issued as LDS-DMA
-// (buffer_load_dwordx4 ... lds) as soon as block b's words are read back,
-// the fused launch's loader (config 3 sequential plan, same box:
-// 0.632-0.634 vs 0.648 ms for the register-prefetching form, 1,424 vs
-// 1,443 VALU per compression, profiles/r04a, r04b); A/B forms: 1 = the
-// register-prefetching block loop (hash_tile_pipelined) with no-yield
-// rounds (variant 11), 2 = the same with the product rounds (round 3's
-// product form, variant 12), 3 = LDS-DMA with the next block's words read
-// back mid-block (variant 13: 0.638 ms, slower).
-template <int kMode>
 __global__ __launch_bounds__(1024, 1) void sha256_msgs_cu_kernel(const uint8_t* __restrict__ arena,
                                                                  uint64_t arena_len,
                                                                  const uint64_t* __restrict__ off,
@@ -914,9 +755,7 @@ __global__ __launch_bounds__(1024, 1) void sha256_msgs_cu_kernel(const uint8_t* 
     const uint32_t wv = threadIdx.x >> 6;
     const uint32_t t = blockIdx.x * (blockDim.x >> 6) + wv;
     if (t * 64u >= n) return;  // whole wave idle (wave-uniform)
-    hash_tile<true, false, false, true, kMode == 1, kMode == 0 || kMode >= 4, kMode == 3,
-              kMode == 4 ? 1 : kMode == 5 ? 2 : 0>(arena, arena_len, off, len, order, n, out, cu_lds + 256u * wv, t,
-                                                     lane);
+    hash_tile<true, false, false, true>(arena, arena_len, off, len, order, n, out, cu_lds + 256u * wv, t, lane);
 }
 
 // ---- overlapped cycles: this cycle's request tiles + the previous cycle's
@@ -2082,11 +1921,13 @@ uint32_t cu_count() {
     return v;
 }
 
-// The dynamic-LDS limit of kernel `fn` (one of 8 forms) raised on the
-// current device, once per (device, form): per-device flags, set with atomics
-// (mirsha_hash_batch_multi launches from one thread per device).
-hipError_t dyn_lds_attr(const void* fn, int form, uint32_t bytes) {
-    static std::atomic<uint8_t> done[64][8] = {};
+// The dynamic-LDS limit of kernel `fn` (one of the three that take dynamic
+// LDS) raised on the current device, once per (device, kernel): per-device
+// flags, set with atomics (mirsha_hash_batch_multi launches from one thread
+// per device).
+enum DynLdsKernel { kDynLdsCu, kDynLdsFused, kDynLdsProbe, kDynLdsKernels };
+hipError_t dyn_lds_attr(const void* fn, DynLdsKernel form, uint32_t bytes) {
+    static std::atomic<uint8_t> done[64][kDynLdsKernels] = {};
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev)) return e;
     if (dev >= 0 && dev < 64 && done[dev][form].load(std::memory_order_acquire)) return hipSuccess;
@@ -2114,38 +1955,13 @@ hipError_t launch_msgs(const uint8_t* arena, uint64_t arena_len, const uint64_t*
         launch_k(sha256_msgs_lowocc_kernel, grid, kBlockThreads, 0, s, arena, arena_len, off, len, order, n, out);
         return hipGetLastError();
     }
-    if (variant == kVariantCu || variant_is_ab_form(variant) ||
-        (variant == kVariantLds && tiles <= kCuMaxWavesPerSimd * 4u * cu_count())) {
+    if (variant == kVariantCu || (variant == kVariantLds && tiles <= kCuMaxWavesPerSimd * 4u * cu_count())) {
         // k waves per SIMD, one workgroup of 4k waves per CU
         const uint32_t k = (tiles + 4u * cu_count() - 1u) / (4u * cu_count());
         const uint32_t wg_waves = 4u * std::min(k, kCuMaxWavesPerSimd);
         const uint32_t cgrid = (tiles + wg_waves - 1u) / wg_waves;
-#ifdef MIRSHA_AB_FORMS
-        // tools/ab_build.sh lib: the retired and diagnostic forms (11-15)
-        const int form = variant == kVariantCuNoYield ? 1 : variant == kVariantCuPrefetch ? 2
-                         : variant == kVariantCuDmaPipe ? 3 : variant == kVariantCuDiagNoLoads ? 4
-                         : variant == kVariantCuDiagNoPrio ? 5 : 0;
-        const void* fns[6] = {(const void*)sha256_msgs_cu_kernel<0>, (const void*)sha256_msgs_cu_kernel<1>,
-                              (const void*)sha256_msgs_cu_kernel<2>, (const void*)sha256_msgs_cu_kernel<3>,
-                              (const void*)sha256_msgs_cu_kernel<4>, (const void*)sha256_msgs_cu_kernel<5>};
-        const int slots[6] = {0, 1, 2, 5, 6, 7};  // dyn_lds_attr forms (3: fused, 4: placement probe)
-        if (hipError_t e = dyn_lds_attr(fns[form], slots[form], kCuLds)) return e;
-        if (form == 4)
-            launch_k(sha256_msgs_cu_kernel<4>, cgrid, 64u * wg_waves, kCuLds, s, arena, arena_len, off, len, order, n, out);
-        else if (form == 5)
-            launch_k(sha256_msgs_cu_kernel<5>, cgrid, 64u * wg_waves, kCuLds, s, arena, arena_len, off, len, order, n, out);
-        else if (form == 1)
-            launch_k(sha256_msgs_cu_kernel<1>, cgrid, 64u * wg_waves, kCuLds, s, arena, arena_len, off, len, order, n, out);
-        else if (form == 2)
-            launch_k(sha256_msgs_cu_kernel<2>, cgrid, 64u * wg_waves, kCuLds, s, arena, arena_len, off, len, order, n, out);
-        else if (form == 3)
-            launch_k(sha256_msgs_cu_kernel<3>, cgrid, 64u * wg_waves, kCuLds, s, arena, arena_len, off, len, order, n, out);
-        else
-#endif
-        {
-            if (hipError_t e = dyn_lds_attr((const void*)sha256_msgs_cu_kernel<0>, 0, kCuLds)) return e;
-            launch_k(sha256_msgs_cu_kernel<0>, cgrid, 64u * wg_waves, kCuLds, s, arena, arena_len, off, len, order, n, out);
-        }
+        if (hipError_t e = dyn_lds_attr((const void*)sha256_msgs_cu_kernel, kDynLdsCu, kCuLds)) return e;
+        launch_k(sha256_msgs_cu_kernel, cgrid, 64u * wg_waves, kCuLds, s, arena, arena_len, off, len, order, n, out);
         return hipGetLastError();
     }
     if (variant == kVariantDirect)
@@ -2223,7 +2039,7 @@ hipError_t launch_chain_pair(const uint8_t* digests, uint32_t n_digests, const u
 hipError_t launch_fused_paced(const FusedArgs& a, uint32_t grid, uint32_t pace, hipStream_t s) {
     if (grid == 0) return hipSuccess;
     if (pace < 1 || pace > kPacedMaxPace || a.n_queues != pace) return hipErrorInvalidValue;
-    if (hipError_t e = dyn_lds_attr((const void*)sha256_fused_paced_kernel, 3, kPacedLds)) return e;
+    if (hipError_t e = dyn_lds_attr((const void*)sha256_fused_paced_kernel, kDynLdsFused, kPacedLds)) return e;
     launch_k(sha256_fused_paced_kernel, grid, 256u * pace, kPacedLds, s, a);
     return hipGetLastError();
 }
@@ -2231,7 +2047,7 @@ hipError_t launch_fused_paced(const FusedArgs& a, uint32_t grid, uint32_t pace, 
 hipError_t launch_placement_probe(uint32_t grid, uint32_t pace, uint32_t* broken, uint32_t test, hipStream_t s) {
     if (grid == 0) return hipSuccess;
     if (pace < 1 || pace > kPacedMaxPace) return hipErrorInvalidValue;
-    if (hipError_t e = dyn_lds_attr((const void*)placement_probe_kernel, 4, kPacedLds)) return e;
+    if (hipError_t e = dyn_lds_attr((const void*)placement_probe_kernel, kDynLdsProbe, kPacedLds)) return e;
     launch_k(placement_probe_kernel, grid, 256u * pace, kPacedLds, s, broken, test);
     return hipGetLastError();
 }

@@ -87,24 +87,6 @@ __device__ __forceinline__ void compress_asm(uint32_t st[8], uint32_t w[16]) {
     for (int i = 0; i < 8; i++) st[i] += s[i];
 }
 
-// compress_asm with work interleaved between its asm statements (hook(k)
-// after statement k, see sha256_rounds_asm.h) and the state updated only on
-// lanes with `live` set: every lane runs the rounds (a wave instruction costs
-// the same at any exec mask), so a hook that stages data for the whole wave
-// never runs under a divergent mask.
-template <bool kNoYield = false, class H>
-__device__ __forceinline__ void compress_asm_hooked(uint32_t st[8], uint32_t w[16], bool live, H hook) {
-    uint32_t s[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) s[i] = st[i];
-    if constexpr (kNoYield)
-        rounds_asm_nonop(s, w, hook);
-    else
-        rounds_asm(s, w, hook);
-#pragma unroll
-    for (int i = 0; i < 8; i++) st[i] = live ? st[i] + s[i] : st[i];
-}
-
 // The wave-uniform scalars of a final block whose words 4..15 are all padding
 // (FIPS 180-4 §5.1.1): u = message bytes in the block (at most 16; negative
 // for the length-only block that follows a block ending in the 0x80 marker),

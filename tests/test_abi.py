@@ -94,11 +94,13 @@ def test_no_gpu_multi_is_an_error_not_a_fallback():
 
 def test_product_library_has_no_ab_kernel_forms():
     """The retired / diagnostic CU-block forms (variants 11-15, one of which
-    skips its loads) are compiled only into the tools A/B build
-    (tools/ab_build.sh lib, -DMIRSHA_AB_FORMS): the product library holds the
-    product instantiation of sha256_msgs_cu_kernel and no other."""
+    skipped its loads) are gone: the library's symbols name exactly one
+    sha256_msgs_cu_kernel, the plain (non-template) product kernel.  Distinct
+    mangled names are counted, not lines: a kernel has a host stub and a
+    descriptor."""
     import subprocess
 
     out = subprocess.run(["nm", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    forms = sorted(set(re.findall(r"sha256_msgs_cu_kernelILi(\d+)E", out)))
-    assert forms == ["0"], forms
+    names = sorted(set(re.findall(r"_ZN6mirsha\d+sha256_msgs_cu_kernel\w*", out)))
+    kernels = sorted({n[: -len(".kd")] if n.endswith(".kd") else n for n in names})
+    assert len(kernels) == 1 and "sha256_msgs_cu_kernelE" in kernels[0], kernels

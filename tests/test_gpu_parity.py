@@ -23,15 +23,8 @@ pytestmark = pytest.mark.gpu
 EMPTY = "e3b0c44298fc1c149afbf4c8996fb92427ae41e4649b934ca495991b7852b855"
 
 
-# A/B kernel forms of the tools build (tools/ab_build.sh lib, loaded through
-# MIRSHA_AB_LIB with MIRSHA_AB=1) join the parametrisation when
-# MIRSHA_TEST_AB_VARIANTS lists them, e.g. "12".  The product library rejects them.
-_AB_VARIANTS = [int(v) for v in os.environ.get("MIRSHA_TEST_AB_VARIANTS", "").split(",") if v.strip()]
-
-
-@pytest.fixture(params=[VARIANT_LDS, VARIANT_DIRECT, VARIANT_LOWOCC, VARIANT_LDS_ONLY, VARIANT_PAIR, VARIANT_CU]
-                + _AB_VARIANTS,
-                ids=["lds", "direct", "lowocc", "lds_only", "pair", "cu"] + [f"ab{v}" for v in _AB_VARIANTS])
+@pytest.fixture(params=[VARIANT_LDS, VARIANT_DIRECT, VARIANT_LOWOCC, VARIANT_LDS_ONLY, VARIANT_PAIR, VARIANT_CU],
+                ids=["lds", "direct", "lowocc", "lds_only", "pair", "cu"])
 def eng(engine, request):
     engine.set_variant(request.param)
     yield engine
@@ -1008,11 +1001,9 @@ def _contiguous(seed, n, bs, listed, max_len):
 
 @pytest.mark.parametrize("variant", [11, 12, 13, 14, 15])
 def test_ab_forms_not_in_product_library(engine, variant, monkeypatch):
-    """Variants 11-15 (retired and diagnostic CU-block forms; 14 skips its
-    loads and writes wrong digests) live only in the tools A/B build: the
-    product library refuses them even with MIRSHA_AB=1."""
-    if os.environ.get("MIRSHA_AB_LIB"):
-        pytest.skip("an A/B build is loaded")
+    """Variants 11-15 (retired and diagnostic CU-block forms; 14 skipped its
+    loads and wrote wrong digests) are in no build: the library refuses them
+    even with MIRSHA_AB=1."""
     monkeypatch.setenv("MIRSHA_AB", "1")
     with pytest.raises(MirshaError) as e:
         engine.set_variant(variant)

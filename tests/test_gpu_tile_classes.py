@@ -66,11 +66,8 @@ pytestmark = pytest.mark.gpu
 FILL = 0xA5
 GUARD_ROWS = 64
 
-# A/B kernel forms of the tools build join the parametrisation when
-# MIRSHA_TEST_AB_VARIANTS lists them (as in test_gpu_parity.py).
-_AB_VARIANTS = [int(v) for v in os.environ.get("MIRSHA_TEST_AB_VARIANTS", "").split(",") if v.strip()]
-_VARIANTS = [VARIANT_LDS, VARIANT_DIRECT, VARIANT_LOWOCC, VARIANT_LDS_ONLY, VARIANT_PAIR, VARIANT_CU] + _AB_VARIANTS
-_VARIANT_IDS = ["lds", "direct", "lowocc", "lds_only", "pair", "cu"] + [f"ab{v}" for v in _AB_VARIANTS]
+_VARIANTS = [VARIANT_LDS, VARIANT_DIRECT, VARIANT_LOWOCC, VARIANT_LDS_ONLY, VARIANT_PAIR, VARIANT_CU]
+_VARIANT_IDS = ["lds", "direct", "lowocc", "lds_only", "pair", "cu"]
 
 
 @pytest.fixture(params=_VARIANTS, ids=_VARIANT_IDS)
