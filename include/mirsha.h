@@ -586,6 +586,53 @@ int mirsha_offsets_device(mirsha_ctx* ctx, const uint32_t* d_len, uint32_t n, ui
 int mirsha_ctx_set_order_mode(mirsha_ctx* ctx, int mode);
 int mirsha_ctx_order_mode(const mirsha_ctx* ctx);
 
+/* ------------------------------------------------- the context's hasher */
+/* The reference's hash function is configuration: `Hasher func() hash.Hash`
+ * of the Processor (processor.go:21,58; used at :134 and :313).  A context
+ * hashes with one of:
+ *   MIRSHA_HASHER_SHA256 (default): sha256.New.  Every call, launch and byte
+ *     is what it is without this setting.
+ *   MIRSHA_HASHER_SHA512_256: sha512.New512_256 (FIPS 180-4 §5.3.6.2, §6.7):
+ *     32-byte digests of 128-byte blocks, so every consumer of digest rows
+ *     (the verify and select kernels, the ring's retirement, the dedup scan,
+ *     the bucket order) works unchanged.
+ * The setting applies to kernels queued by calls made after it; tickets
+ * already published keep the function they were queued with.
+ * Calls that honour it (same validation, messages, routes and
+ * mirsha_ctx_host_profile phases): mirsha_hash_batch, mirsha_hash_slices,
+ * mirsha_hash_slices_dedup, mirsha_digest_lists,
+ * mirsha_hash_requests_then_batches (under SHA-512/256 always the staged
+ * route, whatever MIRSHA_PIPELINE_MODE says); mirsha_verify_batch,
+ * mirsha_verify_slices, mirsha_verify_digest_lists; mirsha_hash_batch_device
+ * (under SHA-512/256 MIRSHA_ERANGE for an arena beyond one buffer descriptor,
+ * 0xFFFFFF00 bytes, or n >= 2^27: there is no 64-bit-addressed SHA-512 form,
+ * and a host call that packs more than that into one launch fails with
+ * MIRSHA_EHIP), mirsha_digest_lists_device; every hashing
+ * submission of the ring (mirsha_submit_slices with and without
+ * MIRSHA_SUBMIT_DEDUP, mirsha_submit_batch, mirsha_submit_slices_expect,
+ * mirsha_submit_batch_expect, mirsha_hash_slices_expect,
+ * mirsha_submit_slices_expect_dedup, mirsha_hash_slices_expect_dedup).
+ * Calls built for SHA-256 only refuse any other hasher at entry with
+ * MIRSHA_EINVAL and a message that names the call and the hasher, ahead of
+ * any other effect (state, ring and tickets stay as they were; there is no
+ * silent SHA-256 and no CPU path): mirsha_pipeline_create / _create_mode,
+ * mirsha_hash_requests_then_batches_device, mirsha_pipeline_overlap_device,
+ * mirsha_chains_absorb / _sum / _commit / _commit_device / _commit_submit /
+ * _commit_submit_device, mirsha_streams_run / _run_device / _submit /
+ * _submit_device / _export / _import.  The mirsha_multi_* forms own their
+ * contexts, which stay SHA-256.
+ * mirsha_ctx_set_hasher: MIRSHA_EINVAL for a NULL context or an unknown value
+ * (processor.go:21,58). */
+#define MIRSHA_HASHER_SHA256 0
+#define MIRSHA_HASHER_SHA512_256 1
+int mirsha_ctx_set_hasher(mirsha_ctx* ctx, int hasher);
+/* The context's hasher (processor.go:21,58); MIRSHA_EINVAL for a NULL context. */
+int mirsha_ctx_hasher(const mirsha_ctx* ctx);
+/* Go's Size() and BlockSize() of a hasher (processor.go:21,58): 32 / 64 for
+ * MIRSHA_HASHER_SHA256, 32 / 128 for MIRSHA_HASHER_SHA512_256.  Host only, no
+ * context; either pointer may be NULL.  MIRSHA_EINVAL: an unknown hasher. */
+int mirsha_hasher_info(int hasher, uint32_t* digest_bytes, uint32_t* block_bytes);
+
 /* ------------------------------------- streaming checkpoint chains (f4) */
 /* Device-resident running SHA-256 states, one per application node: the
  * testengine application's checkpoint value is Sum() of a hash into which

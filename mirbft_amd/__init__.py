@@ -8,9 +8,9 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/mirsha.h.
 from . import eventlog, hashdata, sharding
 from ._lib import MirshaError, MirshaUnavailable
 from .engine import (STREAM_RESET, STREAM_SUM, STREAM_SUM_RESET, STREAM_WRITE, CheckpointChains, CommitTicket, Engine,
-                     ExpectTicket, HashStreams, MultiEngine, SliceArrays, StreamHasher, StreamTicket, Ticket, bucket_order, commit_plan,
+                     ExpectTicket, HASHERS, HashStreams, MultiEngine, SliceArrays, StreamHasher, StreamTicket, Ticket, bucket_order, commit_plan,
                      commit_seg_plan, dedup_plan, dedup_rows, device_count, expect_bitmap, expect_plan, hash_batch_multi,
-                     mismatch_indices, order_plan, stream_plan, stream_seg_plan)
+                     hasher_info, mismatch_indices, order_plan, stream_plan, stream_seg_plan)
 from .processor import (ActionResults, Actions, Checkpoint, CheckpointResult, Commit, CommitBatch, DeviceLog, GpuHash,
                         HashRequest, HashResult, PendingResults, Processor, ProcessorWorkPool, StreamLog,
                         commit_programme, gpu_hasher)
@@ -48,6 +48,8 @@ __all__ = [
     "MirshaError",
     "MirshaUnavailable",
     "bucket_order",
+    "HASHERS",
+    "hasher_info",
     "order_plan",
     "device_count",
     "hash_batch_multi",

@@ -39,6 +39,8 @@ MIRSHA_SUBMIT_DEDUP = 1
 MIRSHA_ORDER_MAX_BINS = 4096
 MIRSHA_ORDER_HOST = 0
 MIRSHA_ORDER_DEVICE = 1
+MIRSHA_HASHER_SHA256 = 0
+MIRSHA_HASHER_SHA512_256 = 1
 
 ERROR_NAMES = {
     MIRSHA_EINVAL: "EINVAL",
@@ -134,6 +136,9 @@ SIGNATURES = {
     "mirsha_offsets_device": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
     "mirsha_ctx_set_order_mode": (c_int, [c_void_p, c_int]),
     "mirsha_ctx_order_mode": (c_int, [c_void_p]),
+    "mirsha_ctx_set_hasher": (c_int, [c_void_p, c_int]),
+    "mirsha_ctx_hasher": (c_int, [c_void_p]),
+    "mirsha_hasher_info": (c_int, [c_int, _u32p, _u32p]),
     "mirsha_pipeline_create": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mirsha_pipeline_create_mode": (
         c_int,

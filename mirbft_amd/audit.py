@@ -34,13 +34,25 @@ class AuditReport:
                            "mismatches": [list(m) for m in self.mismatches]})
 
 
-def audit_log(events: Sequence[eventlog.RecordedEvent], engine, max_bytes: int = 1 << 30) -> AuditReport:
+def audit_log(events: Sequence[eventlog.RecordedEvent], engine, max_bytes: int = 1 << 30,
+              hasher=None) -> AuditReport:
     """Re-hash and verify every reconstructible HashResult of ``events``.
+
+    ``hasher``: the `Hasher` the recording node was configured with
+    (processor.go:21,58), "sha256" or "sha512_256"; the engine hashes with it
+    for this audit and has its own hasher back afterwards.  None: the engine's.
 
     ``engine.verify_slices(requests, expected)`` is called once per at most
     ``max_bytes`` of hash data (a single larger result gets a call of its own).
     A result whose recorded digest is not 32 bytes long is a mismatch without
     device work; a result whose payload was redacted counts as skipped."""
+    if hasher is not None:
+        before = engine.hasher
+        engine.set_hasher(hasher)
+        try:
+            return audit_log(events, engine, max_bytes)
+        finally:
+            engine.set_hasher(before)
     report = AuditReport()
     where: List[Tuple[int, int]] = []
     data: List[List[bytes]] = []
@@ -83,8 +95,19 @@ def audit_log(events: Sequence[eventlog.RecordedEvent], engine, max_bytes: int =
 
 def main(argv: Optional[Sequence[str]] = None, engine=None) -> int:
     args = list(sys.argv[1:] if argv is None else argv)
+    hasher = None
+    if "--hasher" in args:
+        k = args.index("--hasher")
+        if k + 1 < len(args):
+            hasher = args[k + 1]
+        del args[k:k + 2]
+        from .engine import HASHERS
+
+        if hasher not in HASHERS:
+            print(f"--hasher: one of {sorted(HASHERS)}", file=sys.stderr)
+            return 2
     if len(args) != 1:
-        print("usage: python -m mirbft_amd.audit LOG", file=sys.stderr)
+        print("usage: python -m mirbft_amd.audit LOG [--hasher sha256|sha512_256]", file=sys.stderr)
         return 2
     try:
         with open(args[0], "rb") as f:
@@ -98,7 +121,7 @@ def main(argv: Optional[Sequence[str]] = None, engine=None) -> int:
 
         engine = Engine(0)
     try:
-        report = audit_log(events, engine)
+        report = audit_log(events, engine, hasher=hasher)
     except eventlog.EventLogError as e:  # an event that does not parse
         print(json.dumps({"error": str(e)}))
         return 2

@@ -307,10 +307,13 @@ int mirsha_hash_batch_device(mirsha_ctx* c, const uint8_t* d_arena, uint64_t are
     if (!c) return MIRSHA_EINVAL;
     if (n == 0) return MIRSHA_OK;
     if (!d_off || !d_len || !d_out || (!d_arena && arena_len)) return fail(c, MIRSHA_EINVAL, "NULL argument");
+    if (c->hasher == MIRSHA_HASHER_SHA512_256 && (arena_len > mirsha::kMaxBufferArena || n >= mirsha::kMaxBufferMsgs))
+        return fail(c, MIRSHA_ERANGE, "hasher sha512_256: arena_len %llu > %llu or n %u >= %u (one buffer descriptor)",
+                    (unsigned long long)arena_len, (unsigned long long)mirsha::kMaxBufferArena, n,
+                    mirsha::kMaxBufferMsgs);
     if (int rc = use_device(c)) return rc;
     return timed_launch(c, 0, [&] {
-        return mirsha::launch_msgs(d_arena, arena_len, d_off, d_len, d_order, n, d_out, c->variant,
-                                   c->stream);
+        return hasher_launch_msgs(c, d_arena, arena_len, d_off, d_len, d_order, n, d_out, c->stream);
     });
 }
 
@@ -324,8 +327,8 @@ int mirsha_digest_lists_device(mirsha_ctx* c, const uint8_t* d_digests, uint32_t
     if (int rc = use_device(c)) return rc;
     HIP_TRY(c, c->d_scratch.ensure(sizeof(uint32_t) * std::max<uint32_t>(n_entries, 1)));
     return timed_launch(c, 1, [&] {
-        return mirsha::launch_lists(d_digests, n_digests, d_idx, n_entries, d_first, n_lists,
-                                    c->d_scratch.as<uint32_t>(), d_out, c->stream);
+        return hasher_launch_lists(c, d_digests, n_digests, d_idx, n_entries, d_first, n_lists,
+                                   c->d_scratch.as<uint32_t>(), d_out, c->stream);
     });
 }
 
@@ -388,6 +391,23 @@ int mirsha_ctx_set_order_mode(mirsha_ctx* c, int mode) {
 }
 
 int mirsha_ctx_order_mode(const mirsha_ctx* c) { return c ? c->order_mode : MIRSHA_EINVAL; }
+
+int mirsha_ctx_set_hasher(mirsha_ctx* c, int hasher) {
+    if (!c) return MIRSHA_EINVAL;
+    if (mirsha_hasher_info(hasher, nullptr, nullptr) != MIRSHA_OK)
+        return fail(c, MIRSHA_EINVAL, "hasher %d (0 = sha256, 1 = sha512_256)", hasher);
+    c->hasher = hasher;
+    return MIRSHA_OK;
+}
+
+int mirsha_ctx_hasher(const mirsha_ctx* c) { return c ? c->hasher : MIRSHA_EINVAL; }
+
+int mirsha_hasher_info(int hasher, uint32_t* digest_bytes, uint32_t* block_bytes) {
+    if (hasher != MIRSHA_HASHER_SHA256 && hasher != MIRSHA_HASHER_SHA512_256) return MIRSHA_EINVAL;
+    if (digest_bytes) *digest_bytes = 32u;
+    if (block_bytes) *block_bytes = hasher == MIRSHA_HASHER_SHA512_256 ? 128u : 64u;
+    return MIRSHA_OK;
+}
 
 int mirsha_synth_mixed_lengths_device(mirsha_ctx* c, uint64_t seed, uint64_t first, uint64_t count,
                                       uint32_t* d_len) {
@@ -454,6 +474,7 @@ void mirsha_chains_destroy(mirsha_chains* ch) {
 
 int mirsha_chains_absorb(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, const uint32_t* chain_of,
                          uint32_t m) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !ch) return MIRSHA_EINVAL;
     if (m == 0) return MIRSHA_OK;
     if (!digests || !chain_of) return fail(c, MIRSHA_EINVAL, "NULL argument");
@@ -510,6 +531,7 @@ int chains_which(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32
 }  // namespace
 
 int mirsha_chains_sum(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32_t k, uint8_t* out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !ch) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (!out) return fail(c, MIRSHA_EINVAL, "NULL argument");
@@ -593,12 +615,14 @@ static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
 int mirsha_chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, uint32_t n_digests,
                          const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
                          uint32_t* n_values_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return chains_commit(c, ch, digests, false, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
 }
 
 int mirsha_chains_commit_device(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* d_digests, uint32_t n_digests,
                                 const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                 uint8_t* values_out, uint32_t* n_values_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return chains_commit(c, ch, d_digests, true, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
 }
 

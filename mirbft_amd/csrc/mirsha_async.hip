@@ -302,10 +302,10 @@ int async_submit(mirsha_ctx* c, const uint8_t* const* slice_ptr, const uint64_t*
             if (sel && !(gather && row0))
                 if (int rc = expect_h2d(c, sl, *xa, c->stream)) return rc;
             int rc = timed_launch(c, 0, [&] {
-                return mirsha::launch_msgs(dv, bytes, reinterpret_cast<const uint64_t*>(dv + o_off),
-                                           reinterpret_cast<const uint32_t*>(dv + o_len),
-                                           identity ? nullptr : reinterpret_cast<const uint32_t*>(dv + o_ord), m,
-                                           dv + o_dig, c->variant, c->stream);
+                return hasher_launch_msgs(c, dv, bytes, reinterpret_cast<const uint64_t*>(dv + o_off),
+                                          reinterpret_cast<const uint32_t*>(dv + o_len),
+                                          identity ? nullptr : reinterpret_cast<const uint32_t*>(dv + o_ord), m,
+                                          dv + o_dig, c->stream);
             });
             if (rc) return rc;
             if (gather) {
@@ -636,10 +636,10 @@ int async_submit_arena(mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len, 
                     return rc;
             tq[3] = ms_since(t_entry);
             if (int rc = timed_launch(c, 0, [&] {
-                    return mirsha::launch_msgs(dv, bytes, d_off, d_len,
-                                               identity ? nullptr
-                                                        : reinterpret_cast<const uint32_t*>(dv + d_meta + o_ord),
-                                               n, kout && !sel ? kout : dv + d_dig, c->variant, c->stream);
+                    return hasher_launch_msgs(c, dv, bytes, d_off, d_len,
+                                              identity ? nullptr
+                                                       : reinterpret_cast<const uint32_t*>(dv + d_meta + o_ord),
+                                              n, kout && !sel ? kout : dv + d_dig, c->stream);
                 }))
                 return rc;
             tq[4] = ms_since(t_entry);

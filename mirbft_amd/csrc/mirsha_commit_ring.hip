@@ -176,6 +176,7 @@ extern "C" {
 int mirsha_chains_commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, uint32_t n_digests,
                                 const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                 uint8_t* values_out, uint32_t* n_values_out, uint64_t* ticket_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return commit_submit(c, ch, digests, false, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out,
                          ticket_out);
 }
@@ -183,6 +184,7 @@ int mirsha_chains_commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t*
 int mirsha_chains_commit_submit_device(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* d_digests, uint32_t n_digests,
                                        const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                        uint8_t* values_out, uint32_t* n_values_out, uint64_t* ticket_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return commit_submit(c, ch, d_digests, true, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out,
                          ticket_out);
 }

@@ -30,6 +30,8 @@
 //                       expectation / commit / stream plans, a mixed ticket's kept-rows
 //                       walk): unit-tested on the CPU (tests/c)
 //   mirsha_multi.hip    the multi-device drop-in (mirsha_multi_*)
+//   mirsha_sha512.hip   the request and list kernels of the second hasher,
+//                       SHA-512/256 (mirsha_sha512.h; hasher_launch_* below)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
 // Digests[i] by the request's position), unlike ProcessorWorkPool's
@@ -55,6 +57,7 @@
 #include "mirsha_host.h"
 #include "mirsha_device.h"
 #include "mirsha_order.h"
+#include "mirsha_sha512.h"
 
 namespace mirsha {
 // mirsha_expect.hip.  Mixed cycles (mirsha_submit_*_expect): compares the
@@ -251,6 +254,7 @@ struct mirsha_ctx {
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
     int variant = mirsha::kVariantLds;
+    int hasher = MIRSHA_HASHER_SHA256;  // mirsha_ctx_set_hasher: which kernels hasher_launch_* queue
     bool timing = false;
     uint32_t time_mask = 0xFFFFFFFFu;  // kernels timed while timing is on
     std::string err;
@@ -409,6 +413,34 @@ int timed_launch(mirsha_ctx* c, int which, F&& launch) {
     if (e != hipSuccess) return fail(c, MIRSHA_EHIP, "kernel launch: %s", hipGetErrorString(e));
     if (bound) c->timers[which].pending.emplace_back(e0, e1);
     return MIRSHA_OK;
+}
+
+// The context's hasher (mirsha_ctx_set_hasher) decides which kernel a hashing
+// launch queues; the callers pass what launch_msgs / launch_lists take and
+// know nothing else about hashers.  Timing ids 0 and 1 are by role (request
+// kernel, list kernel), so the callers keep them.
+inline hipError_t hasher_launch_msgs(const mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len,
+                                     const uint64_t* off, const uint32_t* len, const uint32_t* order, uint32_t n,
+                                     uint8_t* out, hipStream_t s) {
+    if (c->hasher == MIRSHA_HASHER_SHA512_256)
+        return mirsha::launch_sha512_msgs(arena, arena_len, off, len, order, n, out, s);
+    return mirsha::launch_msgs(arena, arena_len, off, len, order, n, out, c->variant, s);
+}
+inline hipError_t hasher_launch_lists(const mirsha_ctx* c, const uint8_t* digests, uint32_t n_digests,
+                                      const uint32_t* idx, uint32_t n_entries, const uint32_t* first, uint32_t n_lists,
+                                      uint32_t* scratch, uint8_t* out, hipStream_t s) {
+    if (c->hasher == MIRSHA_HASHER_SHA512_256)
+        return mirsha::launch_sha512_lists(digests, n_digests, idx, n_entries, first, n_lists, scratch, out, s);
+    return mirsha::launch_lists(digests, n_digests, idx, n_entries, first, n_lists, scratch, out, s);
+}
+
+inline const char* hasher_name(int hasher) { return hasher == MIRSHA_HASHER_SHA512_256 ? "sha512_256" : "sha256"; }
+
+// The entry guard of a call that is built for SHA-256 only (plans, chains,
+// streams): refused under any other hasher, ahead of any other effect.
+inline int sha256_only(mirsha_ctx* c, const char* call) {
+    if (!c || c->hasher == MIRSHA_HASHER_SHA256) return MIRSHA_OK;  // (a NULL context is the call's own MIRSHA_EINVAL)
+    return fail(c, MIRSHA_EINVAL, "%s: hasher %s is not built for this call", call, hasher_name(c->hasher));
 }
 
 int use_device(mirsha_ctx* c);

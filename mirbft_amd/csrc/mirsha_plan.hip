@@ -498,11 +498,13 @@ extern "C" {
 
 int mirsha_pipeline_create(mirsha_ctx* c, uint32_t n_req, const uint32_t* len, const uint32_t* idx,
                            const uint32_t* list_first, uint32_t n_lists, mirsha_pipeline** out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return mirsha_pipeline_create_mode(c, n_req, len, idx, list_first, n_lists, default_pipeline_mode(), out);
 }
 
 int mirsha_pipeline_create_mode(mirsha_ctx* c, uint32_t n_req, const uint32_t* len, const uint32_t* idx,
                                 const uint32_t* list_first, uint32_t n_lists, int mode, mirsha_pipeline** out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !out) return MIRSHA_EINVAL;
     *out = nullptr;
     if (mode != MIRSHA_PIPELINE_SEQUENTIAL && mode != MIRSHA_PIPELINE_FUSED && mode != MIRSHA_PIPELINE_AUTO)
@@ -579,6 +581,7 @@ int mirsha_pipeline_status(mirsha_ctx* c, mirsha_pipeline* p) {
 int mirsha_hash_requests_then_batches_device(mirsha_ctx* c, mirsha_pipeline* p, const uint8_t* d_arena,
                                              uint64_t arena_len, const uint64_t* d_off, const uint32_t* d_len,
                                              uint8_t* d_req_out, uint8_t* d_batch_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !p) return MIRSHA_EINVAL;
     if (p->device != c->device) return fail(c, MIRSHA_EINVAL, "pipeline built for device %d", p->device);
     if (p->n_req && (!d_off || !d_len || !d_req_out || (!d_arena && arena_len))) return fail(c, MIRSHA_EINVAL, "NULL argument");
@@ -591,6 +594,7 @@ int mirsha_hash_requests_then_batches_device(mirsha_ctx* c, mirsha_pipeline* p, 
 int mirsha_pipeline_overlap_device(mirsha_ctx* c, mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len,
                                    const uint64_t* d_off, const uint32_t* d_len, uint8_t* d_req_out,
                                    const uint8_t* d_prev_req, uint8_t* d_prev_batch_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !p) return MIRSHA_EINVAL;
     if (p->device != c->device) return fail(c, MIRSHA_EINVAL, "pipeline built for device %d", p->device);
     const bool tiles = d_req_out != nullptr && p->n_req;

@@ -409,10 +409,10 @@ int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const
         HIP_TRY(c, hipStreamWaitEvent(c->stream, ev_in[k], 0));
         if (cnt) {
             if (int rc = timed_launch(c, 0, [&] {
-                    return mirsha::launch_msgs(d_arena, total, reinterpret_cast<const uint64_t*>(dm + L.off) + i0,
-                                               reinterpret_cast<const uint32_t*>(dm + L.len) + i0,
-                                               ordered ? reinterpret_cast<const uint32_t*>(dm + L.order) + i0 : nullptr,
-                                               cnt, d_req + 32ull * i0, c->variant, c->stream);
+                    return hasher_launch_msgs(c, d_arena, total, reinterpret_cast<const uint64_t*>(dm + L.off) + i0,
+                                              reinterpret_cast<const uint32_t*>(dm + L.len) + i0,
+                                              ordered ? reinterpret_cast<const uint32_t*>(dm + L.order) + i0 : nullptr,
+                                              cnt, d_req + 32ull * i0, c->stream);
                 }))
                 return rc;
         }
@@ -438,9 +438,9 @@ int run_pipelined(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const
     if (n_lists) {
         HIP_TRY(c, c->d_scratch.ensure(sizeof(uint32_t) * std::max<uint32_t>(entries, 1)));
         if (int rc = timed_launch(c, 1, [&] {
-                return mirsha::launch_lists(d_req, n, reinterpret_cast<const uint32_t*>(dm + L.idx), entries,
-                                            reinterpret_cast<const uint32_t*>(dm + L.first), n_lists,
-                                            c->d_scratch.as<uint32_t>(), d_lst, c->stream);
+                return hasher_launch_lists(c, d_req, n, reinterpret_cast<const uint32_t*>(dm + L.idx), entries,
+                                           reinterpret_cast<const uint32_t*>(dm + L.first), n_lists,
+                                           c->d_scratch.as<uint32_t>(), d_lst, c->stream);
             }))
             return rc;
         HIP_TRY(c, hipEventRecord(ev_lk, c->stream));
@@ -565,10 +565,10 @@ int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const ui
     uint8_t* d_lst = d_req + 32ull * n;
     if (n) {
         if (int rc = timed_launch(c, 0, [&] {
-                return mirsha::launch_msgs(d_arena, src.total, reinterpret_cast<const uint64_t*>(dm + L.off),
-                                           reinterpret_cast<const uint32_t*>(dm + L.len),
-                                           ordered ? reinterpret_cast<const uint32_t*>(dm + L.order) : nullptr, n,
-                                           d_req, c->variant, c->stream);
+                return hasher_launch_msgs(c, d_arena, src.total, reinterpret_cast<const uint64_t*>(dm + L.off),
+                                          reinterpret_cast<const uint32_t*>(dm + L.len),
+                                          ordered ? reinterpret_cast<const uint32_t*>(dm + L.order) : nullptr, n,
+                                          d_req, c->stream);
             }))
             return rc;
     }
@@ -579,9 +579,9 @@ int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const ui
         const uint32_t n_dig = n ? n : (uint32_t)(src.total / 32u);
         HIP_TRY(c, c->d_scratch.ensure(sizeof(uint32_t) * std::max<uint32_t>(entries, 1)));
         if (int rc = timed_launch(c, 1, [&] {
-                return mirsha::launch_lists(d_dig, n_dig, reinterpret_cast<const uint32_t*>(dm + L.idx), entries,
-                                            reinterpret_cast<const uint32_t*>(dm + L.first), n_lists,
-                                            c->d_scratch.as<uint32_t>(), d_lst, c->stream);
+                return hasher_launch_lists(c, d_dig, n_dig, reinterpret_cast<const uint32_t*>(dm + L.idx), entries,
+                                           reinterpret_cast<const uint32_t*>(dm + L.first), n_lists,
+                                           c->d_scratch.as<uint32_t>(), d_lst, c->stream);
             }))
             return rc;
     }
@@ -835,7 +835,9 @@ int mirsha_hash_requests_then_batches(mirsha_ctx* c, const uint8_t* arena, uint6
     // uses a plan only when asked (MIRSHA_PIPELINE_MODE=fused|auto); the
     // device API (mirsha_pipeline_create + *_device) amortises one plan.
     const char* pmode = getenv("MIRSHA_PIPELINE_MODE");
-    const bool pipelined = pmode && (strcmp(pmode, "fused") == 0 || strcmp(pmode, "auto") == 0);
+    // (the plans are SHA-256 only: any other hasher takes the staged route)
+    const bool pipelined = c->hasher == MIRSHA_HASHER_SHA256 && pmode &&
+                           (strcmp(pmode, "fused") == 0 || strcmp(pmode, "auto") == 0);
     uint64_t lo = 0, hi = 0, total = 0;
     if (pipelined) {
         if (int rc = arena_span(c, arena_len, off, len, n_req, &lo, &hi)) return rc;

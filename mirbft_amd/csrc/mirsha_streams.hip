@@ -150,6 +150,7 @@ void mirsha_streams_destroy(mirsha_streams* st) {
 int mirsha_streams_run(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, uint64_t arena_len,
                        const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                        const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return streams_run(c, st, arena, false, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                        n_values_out);
 }
@@ -157,11 +158,13 @@ int mirsha_streams_run(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, 
 int mirsha_streams_run_device(mirsha_ctx* c, mirsha_streams* st, const uint8_t* d_arena, uint64_t arena_len,
                               const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                               const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return streams_run(c, st, d_arena, true, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                        n_values_out);
 }
 
 int mirsha_streams_export(mirsha_ctx* c, mirsha_streams* st, const uint32_t* which, uint32_t k, uint8_t* out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !st) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (int rc = streams_which(c, st, which, k, out)) return rc;
@@ -186,6 +189,7 @@ int mirsha_streams_export(mirsha_ctx* c, mirsha_streams* st, const uint32_t* whi
 }
 
 int mirsha_streams_import(mirsha_ctx* c, mirsha_streams* st, const uint32_t* which, uint32_t k, const uint8_t* in) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !st) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (int rc = streams_which(c, st, which, k, in)) return rc;

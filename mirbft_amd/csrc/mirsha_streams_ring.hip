@@ -198,6 +198,7 @@ int mirsha_streams_submit(mirsha_ctx* c, mirsha_streams* st, const uint8_t* aren
                           const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                           const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
                           uint64_t* ticket_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return streams_submit(c, st, arena, false, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                           n_values_out, ticket_out);
 }
@@ -206,6 +207,7 @@ int mirsha_streams_submit_device(mirsha_ctx* c, mirsha_streams* st, const uint8_
                                  const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                                  const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
                                  uint64_t* ticket_out) {
+    if (int rc = sha256_only(c, __func__)) return rc;
     return streams_submit(c, st, d_arena, true, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                           n_values_out, ticket_out);
 }

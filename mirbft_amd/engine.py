@@ -31,6 +31,8 @@ STREAM_SUM = _lib.MIRSHA_STREAM_SUM
 STREAM_SUM_RESET = _lib.MIRSHA_STREAM_SUM_RESET
 STREAM_RESET = _lib.MIRSHA_STREAM_RESET
 ORDER_MODES = {"host": _lib.MIRSHA_ORDER_HOST, "device": _lib.MIRSHA_ORDER_DEVICE}
+# The Processor's `Hasher` (processor.go:21,58): sha256.New or sha512.New512_256.
+HASHERS = {"sha256": _lib.MIRSHA_HASHER_SHA256, "sha512_256": _lib.MIRSHA_HASHER_SHA512_256}
 ASYNC_SLOTS = 4  # submissions in flight per context (mirsha_submit_slices)
 
 # mirsha_pipeline modes (include/mirsha.h)
@@ -51,6 +53,27 @@ def _ptr(a: np.ndarray | None) -> int | None:
     if a is None:
         return None
     return a.ctypes.data if a.size else None
+
+
+def _hasher_id(hasher: str | int) -> int:
+    """A hasher's id from its name or id; ValueError for an unknown one (no
+    library call)."""
+    if isinstance(hasher, str):
+        if hasher not in HASHERS:
+            raise ValueError(f"hasher {hasher!r}: one of {sorted(HASHERS)}")
+        return HASHERS[hasher]
+    if int(hasher) not in HASHERS.values():
+        raise ValueError(f"hasher {hasher!r}: one of {sorted(HASHERS.values())}")
+    return int(hasher)
+
+
+def hasher_info(hasher: str | int) -> tuple[int, int]:
+    """(digest bytes, block bytes) of a hasher, Go's Size() and BlockSize():
+    (32, 64) for "sha256", (32, 128) for "sha512_256" (mirsha_hasher_info; host
+    only, no device needed)."""
+    size, block = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    check(_lib.load().mirsha_hasher_info(_hasher_id(hasher), ctypes.byref(size), ctypes.byref(block)))
+    return size.value, block.value
 
 
 def _as_u8(buf) -> np.ndarray:
@@ -372,6 +395,23 @@ class Engine:
         if m < 0:
             self._check(m)
         return {v: k for k, v in ORDER_MODES.items()}[m]
+
+    def set_hasher(self, hasher: str | int) -> None:
+        """The hash function of the calls made from now on: "sha256" (default)
+        or "sha512_256" (mirsha_ctx_set_hasher; the reference's `Hasher`,
+        processor.go:21,58).  The hash, verify and ring calls honour it; plans,
+        checkpoint chains and streams are SHA-256 only and raise MirshaError
+        (MIRSHA_EINVAL) under any other hasher.  Tickets already submitted keep
+        the function they were queued with."""
+        hasher = _hasher_id(hasher)
+        self._check(self._lib.mirsha_ctx_set_hasher(self.ctx, hasher))
+
+    @property
+    def hasher(self) -> str:
+        h = self._lib.mirsha_ctx_hasher(self.ctx)
+        if h < 0:
+            self._check(h)
+        return {v: k for k, v in HASHERS.items()}[h]
 
     def set_timing(self, enable: bool) -> None:
         self._check(self._lib.mirsha_ctx_set_timing(self.ctx, 1 if enable else 0))

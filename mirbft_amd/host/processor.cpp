@@ -66,6 +66,13 @@ uint64_t GpuEngine::Submit(const std::vector<const HashRequest*>& reqs, std::vec
     return ticket;
 }
 
+void GpuEngine::SetHasher(int hasher) {
+    int rc = mirsha_ctx_set_hasher(ctx_, hasher);
+    if (rc != MIRSHA_OK) panic(ctx_, rc, "could not set the hasher");
+}
+
+int GpuEngine::Hasher() const { return mirsha_ctx_hasher(ctx_); }
+
 void GpuEngine::Wait(uint64_t ticket) {
     int rc = mirsha_wait(ctx_, ticket);
     if (rc != MIRSHA_OK) panic(ctx_, rc, "could not collect digests");
@@ -305,6 +312,7 @@ extern "C" int mirbft_host_process_ex(int device, const uint8_t* const* data, co
                                       uint32_t err_len) {
     try {
         mirbft::GpuEngine engine(device);
+        if (flags & 8) engine.SetHasher(MIRSHA_HASHER_SHA512_256);
         mirbft::Processor p(engine, (flags & 1) != 0);
         std::vector<mirbft::HashRequest> reqs(n);
         mirbft::Actions a;

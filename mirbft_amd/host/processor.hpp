@@ -116,6 +116,12 @@ public:
     uint64_t Submit(const std::vector<const HashRequest*>& reqs, std::vector<std::array<uint8_t, 32>>& out,
                     bool dedup = false);
     void Wait(uint64_t ticket);
+    // The reference's `Hasher` (processor.go:21,58) of the calls made from now
+    // on: MIRSHA_HASHER_SHA256 (default) or MIRSHA_HASHER_SHA512_256
+    // (mirsha_ctx_set_hasher).  A DeviceLog is SHA-256 only and panics under any
+    // other hasher of its engine: it then needs an engine of its own.
+    void SetHasher(int hasher);
+    int Hasher() const;
     mirsha_ctx* ctx() { return ctx_; }
 
 private:
@@ -221,7 +227,8 @@ int mirbft_host_features(void);
 int mirbft_host_process(int device, const uint8_t* const* data, const uint64_t* len, uint32_t n,
                         uint8_t* digests_out, char* err, uint32_t err_len);
 // flags: bit 0 = dedup, bit 1 = asynchronous (Submit, then Wait), bit 2 =
-// asynchronous with a dropped (never waited) cycle before four more.
+// asynchronous with a dropped (never waited) cycle before four more, bit 3 =
+// the engine's hasher is MIRSHA_HASHER_SHA512_256 (GpuEngine::SetHasher).
 int mirbft_host_process_ex(int device, const uint8_t* const* data, const uint64_t* len, uint32_t n,
                            uint8_t* digests_out, int flags, uint32_t* unique_out, char* err, uint32_t err_len);
 // One cycle's commits through mirbft::Processor with an n_nodes DeviceLog:

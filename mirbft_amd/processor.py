@@ -67,7 +67,7 @@ from typing import Any, Callable, Optional
 import numpy as np
 
 from ._lib import MIRSHA_COMMIT_CHECKPOINT, MIRSHA_NULL_INDEX
-from .engine import STREAM_SUM_RESET, STREAM_WRITE, CheckpointChains, Engine, HashStreams
+from .engine import STREAM_SUM_RESET, STREAM_WRITE, CheckpointChains, Engine, HashStreams, hasher_info
 
 
 @dataclass(eq=False)
@@ -288,14 +288,21 @@ class StreamLog(_CycleLog):
 
 
 class GpuHash:
-    """hash.Hash (Write / Sum / Reset / Size / BlockSize) whose Sum runs on the GPU."""
-
-    size = 32
-    block_size = 64
+    """hash.Hash (Write / Sum / Reset / Size / BlockSize) whose Sum runs on the
+    GPU, with the engine's hasher: ``size`` / ``block_size`` are Go's Size() /
+    BlockSize() of it, 32 / 64 for "sha256" and 32 / 128 for "sha512_256"."""
 
     def __init__(self, engine: Engine):
         self._engine = engine
         self._parts: list[bytes] = []
+
+    @property
+    def size(self) -> int:
+        return hasher_info(self._engine.hasher)[0]
+
+    @property
+    def block_size(self) -> int:
+        return hasher_info(self._engine.hasher)[1]
 
     def write(self, data: bytes) -> int:
         self._parts.append(bytes(data))
@@ -397,8 +404,15 @@ class Processor:
     """Hash stage of mirbft.Processor; batches one Ready() cycle per device call."""
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, dedup: bool = False,
-                 verify_on_device: bool = False, log=None, async_commits: bool = False):
-        """``log``: the application log (p.Log, processor.go:147,163), e.g. a
+                 verify_on_device: bool = False, log=None, async_commits: bool = False, hasher=None):
+        """``hasher``: the reference's ``Hasher`` (processor.go:21,58) by name,
+        "sha256" or "sha512_256"; it is set on the engine (``Engine.set_hasher``)
+        and so holds for every user of that engine.  None leaves the engine's
+        hasher as it is (a new engine: "sha256").  Checkpoint chains and streams
+        are SHA-256 only: with another hasher a ``DeviceLog`` / ``StreamLog`` on
+        the SAME engine raises MirshaError (MIRSHA_EINVAL) at the first commit;
+        such a log needs an engine of its own.
+        ``log``: the application log (p.Log, processor.go:147,163), e.g. a
         ``DeviceLog``: any object whose ``commit_cycle(commits)`` applies one
         cycle's commits and returns one value per checkpoint among them.
         ``async_commits``: ``submit()`` queues the cycle's commits
@@ -407,6 +421,8 @@ class Processor:
         them (``log.collect_cycle``): commitInParallel beside hashInParallel
         (processor.go:447-470).  The ActionResults are the same either way."""
         self.engine = engine if engine is not None else Engine(device)
+        if hasher is not None:
+            self.engine.set_hasher(hasher)
         self.dedup = dedup
         self.verify_on_device = verify_on_device
         self.log = log
@@ -520,8 +536,8 @@ class ProcessorWorkPool(Processor):
 
     def __init__(self, engine: Optional[Engine] = None, device: int = 0, hash_workers: int = 0,
                  transmit_workers: int = 0, dedup: bool = False, verify_on_device: bool = False, log=None,
-                 async_commits: bool = False):
-        super().__init__(engine, device, dedup, verify_on_device, log, async_commits)
+                 async_commits: bool = False, hasher=None):
+        super().__init__(engine, device, dedup, verify_on_device, log, async_commits, hasher)
         self._mutex = threading.Lock()
         self.hash_workers = hash_workers
 
