@@ -612,13 +612,20 @@ int mirsha_ctx_order_mode(const mirsha_ctx* ctx);
  * MIRSHA_SUBMIT_DEDUP, mirsha_submit_batch, mirsha_submit_slices_expect,
  * mirsha_submit_batch_expect, mirsha_hash_slices_expect,
  * mirsha_submit_slices_expect_dedup, mirsha_hash_slices_expect_dedup).
+ * The checkpoint chains carry a hasher of their own, fixed when they are
+ * created (mirsha_chains_create_hasher): mirsha_chains_absorb / _sum /
+ * _commit / _commit_device / _commit_submit / _commit_submit_device are
+ * served when the context's hasher equals the chains', and refused with
+ * MIRSHA_EINVAL and a message that names the call and both hashers when it
+ * does not (a log that hashes with another function than the requests is a
+ * misconfiguration).  A commit ticket keeps the function it was queued with.
  * Calls built for SHA-256 only refuse any other hasher at entry with
- * MIRSHA_EINVAL and a message that names the call and the hasher, ahead of
- * any other effect (state, ring and tickets stay as they were; there is no
- * silent SHA-256 and no CPU path): mirsha_pipeline_create / _create_mode,
+ * MIRSHA_EINVAL and a message that names the call and the hasher.  Either
+ * refusal comes ahead of any other effect (state, ring and tickets stay as
+ * they were; there is no silent SHA-256 and no CPU path).  SHA-256 only:
+ * mirsha_pipeline_create / _create_mode,
  * mirsha_hash_requests_then_batches_device, mirsha_pipeline_overlap_device,
- * mirsha_chains_absorb / _sum / _commit / _commit_device / _commit_submit /
- * _commit_submit_device, mirsha_streams_run / _run_device / _submit /
+ * mirsha_streams_run / _run_device / _submit /
  * _submit_device / _export / _import.  The mirsha_multi_* forms own their
  * contexts, which stay SHA-256.
  * mirsha_ctx_set_hasher: MIRSHA_EINVAL for a NULL context or an unknown value
@@ -634,11 +641,21 @@ int mirsha_ctx_hasher(const mirsha_ctx* ctx);
 int mirsha_hasher_info(int hasher, uint32_t* digest_bytes, uint32_t* block_bytes);
 
 /* ------------------------------------- streaming checkpoint chains (f4) */
-/* Device-resident running SHA-256 states, one per application node: the
+/* Device-resident running hash states, one per application node: the
  * testengine application's checkpoint value is Sum() of a hash into which
  * every committed request digest is written (NodeState.Commit,
  * testengine/recorder.go:213-256: ActiveHash.Write :223, Sum :244) and which
- * restarts at each checkpoint (NodeState.Set, :186-207).
+ * restarts at each checkpoint (NodeState.Set, :186-207).  That log is made
+ * with the node's Hasher, so a chains object has one, fixed at creation:
+ *   mirsha_chains_create: SHA-256 chains, whatever the context's hasher.
+ *   mirsha_chains_create_hasher: chains of `hasher` (MIRSHA_HASHER_*; an
+ *     unknown value is MIRSHA_EINVAL).  SHA-512/256 chains keep h as 8 64-bit
+ *     words, up to three pending digests (four fill a 128-byte block) and the
+ *     digest count.
+ *   mirsha_chains_hasher: the chains' hasher; MIRSHA_EINVAL for NULL.
+ * Every hashing call on the chains (absorb, sum, the commit calls below) needs
+ * a context whose hasher is the chains' own, else MIRSHA_EINVAL ahead of any
+ * other effect; mirsha_chains_reset hashes nothing and is served under either.
  *   mirsha_chains_absorb: ActiveHash.Write(digest) for m 32-byte digests, in
  *     order; digest i goes to chain chain_of[i].  A null request's digest is
  *     empty and its Write changes nothing: leave it out.
@@ -648,6 +665,8 @@ int mirsha_hasher_info(int hasher, uint32_t* digest_bytes, uint32_t* block_bytes
  * Synchronous; chain ids < n_chains (else MIRSHA_EINVAL). */
 typedef struct mirsha_chains mirsha_chains;
 int mirsha_chains_create(mirsha_ctx* ctx, uint32_t n_chains, mirsha_chains** out);
+int mirsha_chains_create_hasher(mirsha_ctx* ctx, uint32_t n_chains, int hasher, mirsha_chains** out);
+int mirsha_chains_hasher(const mirsha_chains* chains);
 void mirsha_chains_destroy(mirsha_chains* chains);
 int mirsha_chains_absorb(mirsha_ctx* ctx, mirsha_chains* chains, const uint8_t* digests, const uint32_t* chain_of,
                          uint32_t m);

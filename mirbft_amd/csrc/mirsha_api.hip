@@ -433,24 +433,40 @@ int mirsha_synth_requests_device(mirsha_ctx* c, uint64_t seed, uint64_t first, u
     return timed_launch(c, 2, [&] { return mirsha::launch_gen_requests(seed, first, count, data_len, d_arena, c->stream); });
 }
 
-int mirsha_chains_create(mirsha_ctx* c, uint32_t n, mirsha_chains** out) {
+int mirsha_chains_create_hasher(mirsha_ctx* c, uint32_t n, int hasher, mirsha_chains** out) {
     if (!c || !out) return MIRSHA_EINVAL;
     *out = nullptr;
+    if (hasher != MIRSHA_HASHER_SHA256 && hasher != MIRSHA_HASHER_SHA512_256)
+        return fail(c, MIRSHA_EINVAL, "unknown hasher %d", hasher);
     if (n == 0) return fail(c, MIRSHA_EINVAL, "n_chains must be > 0");
     if (int rc = use_device(c)) return rc;
     auto* ch = new mirsha_chains();
     ch->device = c->device;
     ch->n = n;
-    std::vector<uint32_t> h(8ull * n);
-    for (uint32_t i = 0; i < n; i++)
-        for (int j = 0; j < 8; j++) h[8ull * i + j] = mirsha::kH0[j];
+    ch->hasher = hasher;
+    // Hasher() for every chain: H0 as the state's own words.
+    std::vector<uint32_t> h32;
+    std::vector<uint64_t> h64;
+    const void* h0 = nullptr;
+    if (hasher == MIRSHA_HASHER_SHA512_256) {
+        h64.resize(8ull * n);
+        mirsha::sha512_chains_h0(h64.data());
+        for (uint32_t i = 1; i < n; i++)
+            for (int j = 0; j < 8; j++) h64[8ull * i + j] = h64[j];
+        h0 = h64.data();
+    } else {
+        h32.resize(8ull * n);
+        for (uint32_t i = 0; i < n; i++)
+            for (int j = 0; j < 8; j++) h32[8ull * i + j] = mirsha::kH0[j];
+        h0 = h32.data();
+    }
     auto up = [&]() -> int {
-        HIP_TRY(c, ch->d_h.ensure(32ull * n));
-        HIP_TRY(c, ch->d_pend.ensure(32ull * n));
-        HIP_TRY(c, ch->d_cnt.ensure(8ull * n));
-        HIP_TRY(c, hipMemcpyAsync(ch->d_h.p, h.data(), 32ull * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemsetAsync(ch->d_pend.p, 0, 32ull * n, c->stream));
-        HIP_TRY(c, hipMemsetAsync(ch->d_cnt.p, 0, 8ull * n, c->stream));
+        HIP_TRY(c, ch->d_h.ensure(chains_h_bytes(ch)));
+        HIP_TRY(c, ch->d_pend.ensure(chains_pend_bytes(ch)));
+        HIP_TRY(c, ch->d_cnt.ensure(chains_cnt_bytes(ch)));
+        HIP_TRY(c, hipMemcpyAsync(ch->d_h.p, h0, chains_h_bytes(ch), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(ch->d_pend.p, 0, chains_pend_bytes(ch), c->stream));
+        HIP_TRY(c, hipMemsetAsync(ch->d_cnt.p, 0, chains_cnt_bytes(ch), c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return MIRSHA_OK;
     };
@@ -461,6 +477,12 @@ int mirsha_chains_create(mirsha_ctx* c, uint32_t n, mirsha_chains** out) {
     *out = ch;
     return MIRSHA_OK;
 }
+
+int mirsha_chains_create(mirsha_ctx* c, uint32_t n, mirsha_chains** out) {
+    return mirsha_chains_create_hasher(c, n, MIRSHA_HASHER_SHA256, out);
+}
+
+int mirsha_chains_hasher(const mirsha_chains* ch) { return ch ? ch->hasher : MIRSHA_EINVAL; }
 
 void mirsha_chains_destroy(mirsha_chains* ch) {
     if (!ch) return;
@@ -474,11 +496,13 @@ void mirsha_chains_destroy(mirsha_chains* ch) {
 
 int mirsha_chains_absorb(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, const uint32_t* chain_of,
                          uint32_t m) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
     if (!c || !ch) return MIRSHA_EINVAL;
     if (m == 0) return MIRSHA_OK;
     if (!digests || !chain_of) return fail(c, MIRSHA_EINVAL, "NULL argument");
     if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
+    if (ch->hasher == MIRSHA_HASHER_SHA512_256 && m > MIRSHA_COMMIT_ENTRY_CHECKPOINT)  // the writes run as plan entries
+        return fail(c, MIRSHA_ERANGE, "%u digests > %u", m, MIRSHA_COMMIT_ENTRY_CHECKPOINT);
     // Group the writes by chain, keeping their order (counting sort).
     std::vector<uint32_t> count(ch->n + 1, 0);
     for (uint32_t i = 0; i < m; i++) {
@@ -506,10 +530,8 @@ int mirsha_chains_absorb(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
     HIP_TRY(c, hipMemcpyAsync(ch->d_act.p, act.data(), 4ull * na, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(ch->d_afirst.p, afirst.data(), 4ull * (na + 1), hipMemcpyHostToDevice, c->stream));
     if (int rc = timed_launch(c, 1, [&] {
-            return mirsha::launch_chains_absorb(ch->d_dig.as<uint8_t>(), ch->d_pos.as<uint32_t>(),
-                                                ch->d_act.as<uint32_t>(), ch->d_afirst.as<uint32_t>(), na,
-                                                ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(),
-                                                ch->d_cnt.as<uint64_t>(), c->stream);
+            return chains_launch_absorb(ch, ch->d_dig.as<uint8_t>(), ch->d_pos.as<uint32_t>(),
+                                        ch->d_act.as<uint32_t>(), ch->d_afirst.as<uint32_t>(), na, c->stream);
         }))
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // host vectors above feed async copies
@@ -531,16 +553,14 @@ int chains_which(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32
 }  // namespace
 
 int mirsha_chains_sum(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32_t k, uint8_t* out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
     if (!c || !ch) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (!out) return fail(c, MIRSHA_EINVAL, "NULL argument");
     if (int rc = chains_which(c, ch, which, k)) return rc;
     HIP_TRY(c, ch->d_out.ensure(32ull * k));
     if (int rc = timed_launch(c, 1, [&] {
-            return mirsha::launch_chains_sum(ch->d_which.as<uint32_t>(), k, ch->d_h.as<uint32_t>(),
-                                             ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(),
-                                             ch->d_out.as<uint8_t>(), c->stream);
+            return chains_launch_sum(ch, ch->d_which.as<uint32_t>(), k, ch->d_out.as<uint8_t>(), c->stream);
         }))
         return rc;
     HIP_TRY(c, hipMemcpyAsync(out, ch->d_out.p, 32ull * k, hipMemcpyDeviceToHost, c->stream));
@@ -553,8 +573,7 @@ int mirsha_chains_reset(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which,
     if (k == 0) return MIRSHA_OK;
     if (int rc = chains_which(c, ch, which, k)) return rc;
     if (int rc = timed_launch(c, 1, [&] {
-            return mirsha::launch_chains_reset(ch->d_which.as<uint32_t>(), k, ch->d_h.as<uint32_t>(),
-                                               ch->d_cnt.as<uint64_t>(), c->stream);
+            return chains_launch_reset(ch, ch->d_which.as<uint32_t>(), k, c->stream);
         }))
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -600,9 +619,8 @@ static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
     HIP_TRY(c, hipMemcpyAsync(ch->d_plan.p, plan, plan_bytes, hipMemcpyHostToDevice, c->stream));
     const uint32_t* d_plan = ch->d_plan.as<uint32_t>();
     if (int r = timed_launch(c, 1, [&] {
-            return mirsha::launch_chains_commit(d_dig, d_plan + o_ent, d_plan, d_plan + o_first, na,
-                                                ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(),
-                                                ch->d_cnt.as<uint64_t>(), ch->d_out.as<uint8_t>(), c->stream);
+            return chains_launch_commit(ch, d_dig, d_plan + o_ent, d_plan, d_plan + o_first, na,
+                                        ch->d_out.as<uint8_t>(), c->stream);
         }))
         return r;
     if (values) HIP_TRY(c, hipMemcpyAsync(values_out, ch->d_out.p, 32ull * values, hipMemcpyDeviceToHost, c->stream));
@@ -615,14 +633,14 @@ static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
 int mirsha_chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, uint32_t n_digests,
                          const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
                          uint32_t* n_values_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
     return chains_commit(c, ch, digests, false, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
 }
 
 int mirsha_chains_commit_device(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* d_digests, uint32_t n_digests,
                                 const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                 uint8_t* values_out, uint32_t* n_values_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
     return chains_commit(c, ch, d_digests, true, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
 }
 

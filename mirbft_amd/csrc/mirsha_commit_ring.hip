@@ -141,9 +141,9 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
     t.owner = &ch->ring;
     t.on_device = on_device;
     t.stage_bytes = o_tab + (on_device ? 0ull : 32ull * n_digests);
-    t.state[0] = {ch->d_h.p, 32ull * ch->n};
-    t.state[1] = {ch->d_pend.p, 32ull * ch->n};
-    t.state[2] = {ch->d_cnt.p, 8ull * ch->n};
+    t.state[0] = {ch->d_h.p, chains_h_bytes(ch)};
+    t.state[1] = {ch->d_pend.p, chains_pend_bytes(ch)};
+    t.state[2] = {ch->d_cnt.p, chains_cnt_bytes(ch)};
     t.values_out = values_out;
     t.timer = 1;
     return seg_submit(
@@ -157,12 +157,10 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
             if (!on_device && n_digests) memcpy(st + o_tab, digests, 32ull * n_digests);
         },
         [&](const uint8_t* dv, const uint8_t* const* state_in, uint8_t* rows, hipStream_t q) {
-            return mirsha::launch_chains_commit_seg(
-                on_device ? digests : dv + o_tab, reinterpret_cast<const uint32_t*>(dv + o_ent),
+            return chains_launch_commit_seg(
+                ch, on_device ? digests : dv + o_tab, reinterpret_cast<const uint32_t*>(dv + o_ent),
                 reinterpret_cast<const uint32_t*>(dv), reinterpret_cast<const uint32_t*>(dv + o_first),
-                reinterpret_cast<const uint32_t*>(dv + o_flags), t.n_seg, reinterpret_cast<const uint32_t*>(state_in[0]),
-                reinterpret_cast<const uint32_t*>(state_in[1]), reinterpret_cast<const uint64_t*>(state_in[2]),
-                ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), rows, commit_seg_prio(), q);
+                reinterpret_cast<const uint32_t*>(dv + o_flags), t.n_seg, state_in, rows, commit_seg_prio(), q);
         },
         n_values_out, ticket_out);
 }
@@ -176,7 +174,7 @@ extern "C" {
 int mirsha_chains_commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, uint32_t n_digests,
                                 const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                 uint8_t* values_out, uint32_t* n_values_out, uint64_t* ticket_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
     return commit_submit(c, ch, digests, false, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out,
                          ticket_out);
 }
@@ -184,7 +182,7 @@ int mirsha_chains_commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t*
 int mirsha_chains_commit_submit_device(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* d_digests, uint32_t n_digests,
                                        const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
                                        uint8_t* values_out, uint32_t* n_values_out, uint64_t* ticket_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
     return commit_submit(c, ch, d_digests, true, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out,
                          ticket_out);
 }

@@ -32,6 +32,8 @@
 //   mirsha_multi.hip    the multi-device drop-in (mirsha_multi_*)
 //   mirsha_sha512.hip   the request and list kernels of the second hasher,
 //                       SHA-512/256 (mirsha_sha512.h; hasher_launch_* below)
+//   mirsha_sha512_chains.hip  its checkpoint-chain kernels
+//                       (mirsha_sha512_chains.h; chains_launch_* below)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
 // Digests[i] by the request's position), unlike ProcessorWorkPool's
@@ -58,6 +60,7 @@
 #include "mirsha_device.h"
 #include "mirsha_order.h"
 #include "mirsha_sha512.h"
+#include "mirsha_sha512_chains.h"
 
 namespace mirsha {
 // mirsha_expect.hip.  Mixed cycles (mirsha_submit_*_expect): compares the
@@ -309,7 +312,9 @@ struct RingOwner {
 struct mirsha_chains {
     int device = 0;
     uint32_t n = 0;
-    DevBuf d_h, d_pend, d_cnt;                        // state
+    int hasher = MIRSHA_HASHER_SHA256;  // fixed at creation: which kernels chains_launch_* queue
+    // state: h / pend / cnt of 32n / 32n / 8n bytes (SHA-256), 64n / 96n / 8n (SHA-512/256)
+    DevBuf d_h, d_pend, d_cnt;
     DevBuf d_dig, d_pos, d_act, d_afirst, d_which, d_out;  // per call
     // mirsha_chains_commit: mirsha_commit_plan's arrays in one block
     // [act | efirst | ent], one H2D copy (kept across calls).
@@ -436,11 +441,84 @@ inline hipError_t hasher_launch_lists(const mirsha_ctx* c, const uint8_t* digest
 
 inline const char* hasher_name(int hasher) { return hasher == MIRSHA_HASHER_SHA512_256 ? "sha512_256" : "sha256"; }
 
-// The entry guard of a call that is built for SHA-256 only (plans, chains,
-// streams): refused under any other hasher, ahead of any other effect.
+// The entry guard of a call that is built for SHA-256 only (plans, streams):
+// refused under any other hasher, ahead of any other effect.
 inline int sha256_only(mirsha_ctx* c, const char* call) {
     if (!c || c->hasher == MIRSHA_HASHER_SHA256) return MIRSHA_OK;  // (a NULL context is the call's own MIRSHA_EINVAL)
     return fail(c, MIRSHA_EINVAL, "%s: hasher %s is not built for this call", call, hasher_name(c->hasher));
+}
+
+// The entry guard of a hashing call on checkpoint chains: served when the
+// context hashes with the chains' own function, else refused ahead of any
+// other effect (a log that hashes with another function than the requests is
+// a misconfiguration).
+inline int chains_hasher_match(mirsha_ctx* c, const mirsha_chains* ch, const char* call) {
+    if (!c || !ch || c->hasher == ch->hasher) return MIRSHA_OK;  // (NULL is the call's own MIRSHA_EINVAL)
+    return fail(c, MIRSHA_EINVAL, "%s: the chains hash with %s, the context with %s", call, hasher_name(ch->hasher),
+                hasher_name(c->hasher));
+}
+
+// The chains' hasher decides which kernel a chains launch queues, as
+// hasher_launch_* do by the context's; the callers pass what launch_chains_*
+// take and know nothing else about hashers.  What differs between the hashers
+// is the state's word type and size alone.
+inline uint64_t chains_h_bytes(const mirsha_chains* ch) {
+    return (ch->hasher == MIRSHA_HASHER_SHA512_256 ? 64ull : 32ull) * ch->n;
+}
+inline uint64_t chains_pend_bytes(const mirsha_chains* ch) {
+    return (ch->hasher == MIRSHA_HASHER_SHA512_256 ? 96ull : 32ull) * ch->n;
+}
+inline uint64_t chains_cnt_bytes(const mirsha_chains* ch) { return 8ull * ch->n; }
+
+inline hipError_t chains_launch_commit(const mirsha_chains* ch, const uint8_t* digests, const uint32_t* ent,
+                                       const uint32_t* act, const uint32_t* efirst, uint32_t n_active, uint8_t* out,
+                                       hipStream_t s) {
+    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
+        return mirsha::launch_sha512_chains_commit(digests, ent, act, efirst, n_active, ch->d_h.as<uint64_t>(),
+                                                   ch->d_pend.as<uint64_t>(), ch->d_cnt.as<uint64_t>(), out, s);
+    return mirsha::launch_chains_commit(digests, ent, act, efirst, n_active, ch->d_h.as<uint32_t>(),
+                                        ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), out, s);
+}
+// mirsha_chains_absorb's grouped writes.  Under SHA-512/256 they are a commit
+// programme without checkpoints (pos = the entries), run by the commit kernel.
+inline hipError_t chains_launch_absorb(const mirsha_chains* ch, const uint8_t* digests, const uint32_t* pos,
+                                       const uint32_t* act, const uint32_t* afirst, uint32_t n_active, hipStream_t s) {
+    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
+        return mirsha::launch_sha512_chains_commit(digests, pos, act, afirst, n_active, ch->d_h.as<uint64_t>(),
+                                                   ch->d_pend.as<uint64_t>(), ch->d_cnt.as<uint64_t>(), nullptr, s);
+    return mirsha::launch_chains_absorb(digests, pos, act, afirst, n_active, ch->d_h.as<uint32_t>(),
+                                        ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), s);
+}
+inline hipError_t chains_launch_sum(const mirsha_chains* ch, const uint32_t* which, uint32_t k, uint8_t* out,
+                                    hipStream_t s) {
+    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
+        return mirsha::launch_sha512_chains_sum(which, k, ch->d_h.as<uint64_t>(), ch->d_pend.as<uint64_t>(),
+                                                ch->d_cnt.as<uint64_t>(), out, s);
+    return mirsha::launch_chains_sum(which, k, ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(),
+                                     ch->d_cnt.as<uint64_t>(), out, s);
+}
+inline hipError_t chains_launch_reset(const mirsha_chains* ch, const uint32_t* which, uint32_t k, hipStream_t s) {
+    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
+        return mirsha::launch_sha512_chains_reset(which, k, ch->d_h.as<uint64_t>(), ch->d_cnt.as<uint64_t>(), s);
+    return mirsha::launch_chains_reset(which, k, ch->d_h.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), s);
+}
+// state_in[0..3): where FIRST lanes read h / pend / cnt (the chains' arrays or
+// the ticket's snapshot of them).
+inline hipError_t chains_launch_commit_seg(const mirsha_chains* ch, const uint8_t* digests, const uint32_t* ent,
+                                           const uint32_t* seg_chain, const uint32_t* sfirst, const uint32_t* seg_flags,
+                                           uint32_t n_seg, const uint8_t* const* state_in, uint8_t* out, uint32_t prio,
+                                           hipStream_t s) {
+    const uint64_t* cnt_in = reinterpret_cast<const uint64_t*>(state_in[2]);
+    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
+        return mirsha::launch_sha512_chains_commit_seg(
+            digests, ent, seg_chain, sfirst, seg_flags, n_seg, reinterpret_cast<const uint64_t*>(state_in[0]),
+            reinterpret_cast<const uint64_t*>(state_in[1]), cnt_in, ch->d_h.as<uint64_t>(), ch->d_pend.as<uint64_t>(),
+            ch->d_cnt.as<uint64_t>(), out, prio, s);
+    return mirsha::launch_chains_commit_seg(digests, ent, seg_chain, sfirst, seg_flags, n_seg,
+                                            reinterpret_cast<const uint32_t*>(state_in[0]),
+                                            reinterpret_cast<const uint32_t*>(state_in[1]), cnt_in,
+                                            ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(),
+                                            out, prio, s);
 }
 
 int use_device(mirsha_ctx* c);

@@ -399,10 +399,12 @@ class Engine:
     def set_hasher(self, hasher: str | int) -> None:
         """The hash function of the calls made from now on: "sha256" (default)
         or "sha512_256" (mirsha_ctx_set_hasher; the reference's `Hasher`,
-        processor.go:21,58).  The hash, verify and ring calls honour it; plans,
-        checkpoint chains and streams are SHA-256 only and raise MirshaError
-        (MIRSHA_EINVAL) under any other hasher.  Tickets already submitted keep
-        the function they were queued with."""
+        processor.go:21,58).  The hash, verify and ring calls honour it.
+        Checkpoint chains carry the hasher they were created with
+        (CheckpointChains, DeviceLog) and raise MirshaError (MIRSHA_EINVAL)
+        while the engine hashes with another one; plans and streams are
+        SHA-256 only and raise under any other hasher.  Tickets already
+        submitted keep the function they were queued with."""
         hasher = _hasher_id(hasher)
         self._check(self._lib.mirsha_ctx_set_hasher(self.ctx, hasher))
 
@@ -908,20 +910,34 @@ class _StateObject:
 
 class CheckpointChains(_StateObject):
     """Streaming checkpoint chains on the device (mirsha_chains_*): one running
-    SHA-256 per application node, as testengine's NodeState.ActiveHash
+    hash per application node, as testengine's NodeState.ActiveHash
     (testengine/recorder.go:186-256).  write() = ActiveHash.Write of committed
     request digests, sum() = ActiveHash.Sum(nil) (state unchanged),
-    reset() = NodeState.Set's fresh hasher."""
+    reset() = NodeState.Set's fresh hasher.
+
+    The chains hash with ``hasher`` ("sha256" or "sha512_256"), fixed here;
+    ``None`` takes the engine's hasher as it is now.  Every call but reset()
+    raises MirshaError (MIRSHA_EINVAL) while the engine hashes with another
+    function: a log that hashes differently from the requests is a
+    misconfiguration."""
 
     _VALUES, _DESTROY = ("commit", "checkpoints"), "mirsha_chains_destroy"
 
-    def __init__(self, engine: Engine, n_chains: int):
+    def __init__(self, engine: Engine, n_chains: int, hasher: str | int | None = None):
         self._engine = engine
         self._lib = engine._lib
+        hid = _hasher_id(engine.hasher if hasher is None else hasher)
         h = ctypes.c_void_p()
-        engine._check(self._lib.mirsha_chains_create(engine.ctx, int(n_chains), ctypes.byref(h)))
+        engine._check(self._lib.mirsha_chains_create_hasher(engine.ctx, int(n_chains), hid, ctypes.byref(h)))
         self.handle = h
         self.n = int(n_chains)
+
+    @property
+    def hasher(self) -> str:
+        h = self._lib.mirsha_chains_hasher(self.handle)
+        if h < 0:
+            self._engine._check(h)
+        return {v: k for k, v in HASHERS.items()}[h]
 
     def write(self, digests, chain_of) -> None:
         d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)

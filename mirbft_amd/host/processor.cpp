@@ -132,7 +132,8 @@ std::vector<CheckpointResult> checkpoint_results(const std::vector<const Commit*
 DeviceLog::DeviceLog(GpuEngine& engine, uint32_t n_nodes, uint32_t node)
     : engine_(engine), n_nodes_(n_nodes), node_(node) {
     if (node >= n_nodes) throw std::runtime_error("DeviceLog: node out of range");
-    int rc = mirsha_chains_create(engine.ctx(), n_nodes, &chains_);
+    // the log is made with the node's Hasher (recorder.go:186-256)
+    int rc = mirsha_chains_create_hasher(engine.ctx(), n_nodes, engine.Hasher(), &chains_);
     if (rc != MIRSHA_OK) panic(engine.ctx(), rc, "could not create the checkpoint chains");
 }
 
@@ -300,7 +301,7 @@ ActionResults PendingResults::Wait() {
 
 }  // namespace mirbft
 
-extern "C" int mirbft_host_features(void) { return 1; }
+extern "C" int mirbft_host_features(void) { return 1 | 2; }
 
 extern "C" int mirbft_host_process(int device, const uint8_t* const* data, const uint64_t* len, uint32_t n,
                                    uint8_t* digests_out, char* err, uint32_t err_len) {
@@ -358,6 +359,7 @@ extern "C" int mirbft_host_commit(int device, uint32_t n_nodes, const uint8_t* c
                                   uint32_t* n_checkpoints_out, int flags, char* err, uint32_t err_len) {
     try {
         mirbft::GpuEngine engine(device);
+        if (flags & 8) engine.SetHasher(MIRSHA_HASHER_SHA512_256);  // before the log is made: it takes the engine's
         mirbft::DeviceLog log(engine, n_nodes);
         mirbft::Processor p(engine, false, &log, (flags & 4) != 0);
         std::vector<mirbft::CommitBatch> batches(n_commits);

@@ -118,8 +118,9 @@ public:
     void Wait(uint64_t ticket);
     // The reference's `Hasher` (processor.go:21,58) of the calls made from now
     // on: MIRSHA_HASHER_SHA256 (default) or MIRSHA_HASHER_SHA512_256
-    // (mirsha_ctx_set_hasher).  A DeviceLog is SHA-256 only and panics under any
-    // other hasher of its engine: it then needs an engine of its own.
+    // (mirsha_ctx_set_hasher).  A DeviceLog takes the engine's hasher when it is
+    // made: set the hasher first.  A log made under another hasher than the
+    // engine has at a commit panics there.
     void SetHasher(int hasher);
     int Hasher() const;
     mirsha_ctx* ctx() { return ctx_; }
@@ -135,7 +136,9 @@ std::unique_ptr<Hash> NewGpuSha256(GpuEngine& engine);
 // stand (processor.go:147,163), the testengine application's state
 // (NodeState.ActiveHash, recorder.go:186-256) in a mirsha_chains.  n_nodes = 1:
 // a node's own log (chain 0); n_nodes > 1: a testengine-style log, all nodes
-// commit the cycle's entries (the digest table is passed once).
+// commit the cycle's entries (the digest table is passed once).  The chains
+// hash with the engine's Hasher() as it is at construction
+// (mirsha_chains_create_hasher).
 class DeviceLog {
 public:
     explicit DeviceLog(GpuEngine& engine, uint32_t n_nodes = 1, uint32_t node = 0);
@@ -220,7 +223,8 @@ private:
 
 extern "C" {
 // What this build of the mirror offers beyond the first C entries: bit 0 = the
-// Processor's async_commits option (bit 2 of mirbft_host_commit's flags).
+// Processor's async_commits option (bit 2 of mirbft_host_commit's flags), bit 1
+// = the log's hasher (bit 3 of mirbft_host_commit's flags).
 int mirbft_host_features(void);
 // Small C entry for tests: hash n single-slice requests through
 // mirbft::Processor (exercises the C++ mirror end to end).
@@ -237,7 +241,8 @@ int mirbft_host_process_ex(int device, const uint8_t* const* data, const uint64_
 // a checkpoint if batch_len[i] == UINT32_MAX.  values_out: 32 bytes per
 // checkpoint and node (row checkpoint * n_nodes + node); flags bit 1 =
 // asynchronous (Submit, then Wait), bit 2 = the Processor's async_commits
-// option (with bit 1: the commits are a ring ticket of their own).
+// option (with bit 1: the commits are a ring ticket of their own), bit 3 =
+// the engine's hasher, and so the log's, is MIRSHA_HASHER_SHA512_256.
 int mirbft_host_commit(int device, uint32_t n_nodes, const uint8_t* const* digest_ptr, const uint32_t* batch_len,
                        uint32_t n_commits, uint8_t* values_out, uint32_t* n_checkpoints_out, int flags, char* err,
                        uint32_t err_len);

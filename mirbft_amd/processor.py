@@ -221,10 +221,17 @@ class DeviceLog(_CycleLog):
     a ticket of the engine's ring): the cycle is queued and the call returns;
     ``collect_cycle(ticket)`` waits for it and returns what ``commit_cycle``
     would have.  Cycles take effect in submission order, whatever the order
-    they are collected in."""
+    they are collected in.
 
-    def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, chains=None):
-        super().__init__(engine, n_nodes, node, chains, CheckpointChains)
+    The testengine log is made with the node's ``Hasher`` (recorder.go:186-256),
+    so the chains hash with ``hasher`` ("sha256" or "sha512_256"; None: the
+    engine's hasher as it is when the log is made).  Make the log after the
+    engine's hasher is set (``Processor(engine, hasher=...)``): a log whose
+    chains hash with another function than the engine raises MirshaError
+    (MIRSHA_EINVAL) at the first commit."""
+
+    def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, chains=None, hasher=None):
+        super().__init__(engine, n_nodes, node, chains, lambda eng, n: CheckpointChains(eng, n, hasher))
         self.chains = self._state
         self._run, self._submit = self.chains.commit, self.chains.submit_commit
 
@@ -408,10 +415,13 @@ class Processor:
         """``hasher``: the reference's ``Hasher`` (processor.go:21,58) by name,
         "sha256" or "sha512_256"; it is set on the engine (``Engine.set_hasher``)
         and so holds for every user of that engine.  None leaves the engine's
-        hasher as it is (a new engine: "sha256").  Checkpoint chains and streams
-        are SHA-256 only: with another hasher a ``DeviceLog`` / ``StreamLog`` on
-        the SAME engine raises MirshaError (MIRSHA_EINVAL) at the first commit;
-        such a log needs an engine of its own.
+        hasher as it is (a new engine: "sha256").  A ``DeviceLog`` takes the
+        engine's hasher when it is made, so one made AFTER this Processor (and
+        set as its ``log``) hashes its checkpoints with the same function,
+        synchronously and with ``async_commits``; one made while the engine
+        still hashed with another function raises MirshaError (MIRSHA_EINVAL)
+        at the first commit.  Streams are SHA-256 only: a ``StreamLog`` on the
+        same engine raises at the first commit under any other hasher.
         ``log``: the application log (p.Log, processor.go:147,163), e.g. a
         ``DeviceLog``: any object whose ``commit_cycle(commits)`` applies one
         cycle's commits and returns one value per checkpoint among them.
