@@ -1,8 +1,8 @@
 // mirsha_api.hip — host side of the C-ABI declared in include/mirsha.h:
 // contexts, timing, the device-pointer API (the digest compare of
 // mirsha_verify_* among it, and the bucket order and the offsets built on the
-// device), synthetic streams, streaming checkpoint chains and the clock probe.  The other host units are listed in
-// mirsha_ctx.h.
+// device), synthetic streams and the clock probe.  The other host units are
+// listed in mirsha_ctx.h.
 #include "mirsha_ctx.h"
 
 namespace mirsha_api {
@@ -126,23 +126,6 @@ int queue_bucket_order(mirsha_ctx* c, const OrderShape& sh, const uint32_t* d_le
         return mirsha::launch_order_scatter(d_len, n, sh.bmax, sh.bins, sh.chunk, sh.n_chunks, base, d_order,
                                             c->stream);
     });
-}
-
-int commit_args(mirsha_ctx* c, const mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
-                const uint32_t* op_chain, const uint32_t* op_digest) {
-    if (!op_chain || !op_digest) return fail(c, MIRSHA_EINVAL, "NULL argument");
-    if (n_digests && !digests) return fail(c, MIRSHA_EINVAL, "NULL digest table (%u digests)", n_digests);
-    if (on_device && (reinterpret_cast<uintptr_t>(digests) & 15u))
-        return fail(c, MIRSHA_EINVAL, "d_digests must be 16-byte aligned");
-    if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
-    return MIRSHA_OK;
-}
-
-int commit_plan_failed(mirsha_ctx* c, int rc, uint32_t bad, const mirsha_chains* ch, uint32_t n_digests,
-                       const uint32_t* op_chain, const uint32_t* op_digest) {
-    if (bad == UINT32_MAX) return fail(c, rc, "commit plan failed");
-    if (op_chain[bad] >= ch->n) return fail(c, rc, "op_chain[%u] = %u >= %u", bad, op_chain[bad], ch->n);
-    return fail(c, rc, "op_digest[%u] = %u >= %u", bad, op_digest[bad], n_digests);
 }
 
 }  // namespace mirsha_api
@@ -431,217 +414,6 @@ int mirsha_synth_requests_device(mirsha_ctx* c, uint64_t seed, uint64_t first, u
     if (count && !d_arena) return fail(c, MIRSHA_EINVAL, "NULL arena");
     if (int rc = use_device(c)) return rc;
     return timed_launch(c, 2, [&] { return mirsha::launch_gen_requests(seed, first, count, data_len, d_arena, c->stream); });
-}
-
-int mirsha_chains_create_hasher(mirsha_ctx* c, uint32_t n, int hasher, mirsha_chains** out) {
-    if (!c || !out) return MIRSHA_EINVAL;
-    *out = nullptr;
-    if (hasher != MIRSHA_HASHER_SHA256 && hasher != MIRSHA_HASHER_SHA512_256)
-        return fail(c, MIRSHA_EINVAL, "unknown hasher %d", hasher);
-    if (n == 0) return fail(c, MIRSHA_EINVAL, "n_chains must be > 0");
-    if (int rc = use_device(c)) return rc;
-    auto* ch = new mirsha_chains();
-    ch->device = c->device;
-    ch->n = n;
-    ch->hasher = hasher;
-    // Hasher() for every chain: H0 as the state's own words.
-    std::vector<uint32_t> h32;
-    std::vector<uint64_t> h64;
-    const void* h0 = nullptr;
-    if (hasher == MIRSHA_HASHER_SHA512_256) {
-        h64.resize(8ull * n);
-        mirsha::sha512_chains_h0(h64.data());
-        for (uint32_t i = 1; i < n; i++)
-            for (int j = 0; j < 8; j++) h64[8ull * i + j] = h64[j];
-        h0 = h64.data();
-    } else {
-        h32.resize(8ull * n);
-        for (uint32_t i = 0; i < n; i++)
-            for (int j = 0; j < 8; j++) h32[8ull * i + j] = mirsha::kH0[j];
-        h0 = h32.data();
-    }
-    auto up = [&]() -> int {
-        HIP_TRY(c, ch->d_h.ensure(chains_h_bytes(ch)));
-        HIP_TRY(c, ch->d_pend.ensure(chains_pend_bytes(ch)));
-        HIP_TRY(c, ch->d_cnt.ensure(chains_cnt_bytes(ch)));
-        HIP_TRY(c, hipMemcpyAsync(ch->d_h.p, h0, chains_h_bytes(ch), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemsetAsync(ch->d_pend.p, 0, chains_pend_bytes(ch), c->stream));
-        HIP_TRY(c, hipMemsetAsync(ch->d_cnt.p, 0, chains_cnt_bytes(ch), c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return MIRSHA_OK;
-    };
-    if (int rc = up()) {
-        mirsha_chains_destroy(ch);
-        return rc;
-    }
-    *out = ch;
-    return MIRSHA_OK;
-}
-
-int mirsha_chains_create(mirsha_ctx* c, uint32_t n, mirsha_chains** out) {
-    return mirsha_chains_create_hasher(c, n, MIRSHA_HASHER_SHA256, out);
-}
-
-int mirsha_chains_hasher(const mirsha_chains* ch) { return ch ? ch->hasher : MIRSHA_EINVAL; }
-
-void mirsha_chains_destroy(mirsha_chains* ch) {
-    if (!ch) return;
-    (void)hipSetDevice(ch->device);
-    owner_retire(ch->ring);
-    for (DevBuf* b : {&ch->d_h, &ch->d_pend, &ch->d_cnt, &ch->d_dig, &ch->d_pos, &ch->d_act, &ch->d_afirst,
-                      &ch->d_which, &ch->d_out, &ch->d_plan})
-        b->release();
-    delete ch;
-}
-
-int mirsha_chains_absorb(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, const uint32_t* chain_of,
-                         uint32_t m) {
-    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
-    if (!c || !ch) return MIRSHA_EINVAL;
-    if (m == 0) return MIRSHA_OK;
-    if (!digests || !chain_of) return fail(c, MIRSHA_EINVAL, "NULL argument");
-    if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
-    if (ch->hasher == MIRSHA_HASHER_SHA512_256 && m > MIRSHA_COMMIT_ENTRY_CHECKPOINT)  // the writes run as plan entries
-        return fail(c, MIRSHA_ERANGE, "%u digests > %u", m, MIRSHA_COMMIT_ENTRY_CHECKPOINT);
-    // Group the writes by chain, keeping their order (counting sort).
-    std::vector<uint32_t> count(ch->n + 1, 0);
-    for (uint32_t i = 0; i < m; i++) {
-        if (chain_of[i] >= ch->n) return fail(c, MIRSHA_EINVAL, "chain_of[%u] = %u >= %u", i, chain_of[i], ch->n);
-        count[chain_of[i] + 1]++;
-    }
-    std::vector<uint32_t> act, afirst(1, 0);
-    for (uint32_t k = 0; k < ch->n; k++)
-        if (count[k + 1]) {
-            act.push_back(k);
-            afirst.push_back(afirst.back() + count[k + 1]);
-        }
-    for (uint32_t k = 0; k < ch->n; k++) count[k + 1] += count[k];
-    std::vector<uint32_t> pos(m);
-    for (uint32_t i = 0; i < m; i++) pos[count[chain_of[i]]++] = i;
-    if (int rc = use_device(c)) return rc;
-    if (int rc = owner_order(c, ch->ring)) return rc;
-    const uint32_t na = (uint32_t)act.size();
-    HIP_TRY(c, ch->d_dig.ensure(32ull * m));
-    HIP_TRY(c, ch->d_pos.ensure(4ull * m));
-    HIP_TRY(c, ch->d_act.ensure(4ull * na));
-    HIP_TRY(c, ch->d_afirst.ensure(4ull * (na + 1)));
-    HIP_TRY(c, hipMemcpyAsync(ch->d_dig.p, digests, 32ull * m, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ch->d_pos.p, pos.data(), 4ull * m, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ch->d_act.p, act.data(), 4ull * na, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(ch->d_afirst.p, afirst.data(), 4ull * (na + 1), hipMemcpyHostToDevice, c->stream));
-    if (int rc = timed_launch(c, 1, [&] {
-            return chains_launch_absorb(ch, ch->d_dig.as<uint8_t>(), ch->d_pos.as<uint32_t>(),
-                                        ch->d_act.as<uint32_t>(), ch->d_afirst.as<uint32_t>(), na, c->stream);
-        }))
-        return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // host vectors above feed async copies
-    return MIRSHA_OK;
-}
-
-namespace {
-int chains_which(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32_t k) {
-    if (!which) return fail(c, MIRSHA_EINVAL, "NULL argument");
-    if (ch->device != c->device) return fail(c, MIRSHA_EINVAL, "chains belong to another device");
-    for (uint32_t j = 0; j < k; j++)
-        if (which[j] >= ch->n) return fail(c, MIRSHA_EINVAL, "which[%u] = %u >= %u", j, which[j], ch->n);
-    if (int rc = use_device(c)) return rc;
-    if (int rc = owner_order(c, ch->ring)) return rc;
-    HIP_TRY(c, ch->d_which.ensure(4ull * k));
-    HIP_TRY(c, hipMemcpyAsync(ch->d_which.p, which, 4ull * k, hipMemcpyHostToDevice, c->stream));
-    return MIRSHA_OK;
-}
-}  // namespace
-
-int mirsha_chains_sum(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32_t k, uint8_t* out) {
-    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
-    if (!c || !ch) return MIRSHA_EINVAL;
-    if (k == 0) return MIRSHA_OK;
-    if (!out) return fail(c, MIRSHA_EINVAL, "NULL argument");
-    if (int rc = chains_which(c, ch, which, k)) return rc;
-    HIP_TRY(c, ch->d_out.ensure(32ull * k));
-    if (int rc = timed_launch(c, 1, [&] {
-            return chains_launch_sum(ch, ch->d_which.as<uint32_t>(), k, ch->d_out.as<uint8_t>(), c->stream);
-        }))
-        return rc;
-    HIP_TRY(c, hipMemcpyAsync(out, ch->d_out.p, 32ull * k, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return MIRSHA_OK;
-}
-
-int mirsha_chains_reset(mirsha_ctx* c, mirsha_chains* ch, const uint32_t* which, uint32_t k) {
-    if (!c || !ch) return MIRSHA_EINVAL;
-    if (k == 0) return MIRSHA_OK;
-    if (int rc = chains_which(c, ch, which, k)) return rc;
-    if (int rc = timed_launch(c, 1, [&] {
-            return chains_launch_reset(ch, ch->d_which.as<uint32_t>(), k, c->stream);
-        }))
-        return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return MIRSHA_OK;
-}
-
-namespace {
-static_assert(mirsha::kCommitEntryCheckpoint == MIRSHA_COMMIT_ENTRY_CHECKPOINT, "plan entry flag");
-
-// Both forms of mirsha_chains_commit: the plan (every check, on the host,
-// before anything is queued), the digest table (uploaded once if it is host
-// memory), the plan block in one copy, one launch, the values back.
-static int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
-                  const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
-                  uint32_t* n_values_out) {
-    if (!c || !ch || !n_values_out) return MIRSHA_EINVAL;
-    *n_values_out = 0;
-    if (n_ops == 0) return MIRSHA_OK;
-    if (int r = commit_args(c, ch, digests, on_device, n_digests, op_chain, op_digest)) return r;
-    const uint32_t cap = std::min(n_ops, ch->n);  // active chains at most
-    const size_t o_first = cap, o_ent = 2ull * cap + 1u;
-    ch->plan.resize(o_ent + n_ops);
-    uint32_t* plan = ch->plan.data();
-    uint32_t na = 0, entries = 0, values = 0, bad = UINT32_MAX;
-    const int rc = mirsha_commit_plan(op_chain, op_digest, n_ops, ch->n, n_digests, plan, plan + o_first, plan + o_ent,
-                                      &na, &entries, &values, &bad);
-    if (rc == MIRSHA_ERANGE)
-        return fail(c, rc, "%u ops / %u digests > %u", n_ops, n_digests, MIRSHA_COMMIT_ENTRY_CHECKPOINT);
-    if (rc != MIRSHA_OK) return commit_plan_failed(c, rc, bad, ch, n_digests, op_chain, op_digest);
-    if (values && !values_out) return fail(c, MIRSHA_EINVAL, "NULL values_out (%u checkpoints)", values);
-    if (na == 0) return MIRSHA_OK;  // null writes only
-    if (int r = use_device(c)) return r;
-    if (int r = owner_order(c, ch->ring)) return r;
-    const uint8_t* d_dig = digests;
-    if (!on_device && n_digests) {
-        HIP_TRY(c, ch->d_dig.ensure(32ull * n_digests));
-        HIP_TRY(c, hipMemcpyAsync(ch->d_dig.p, digests, 32ull * n_digests, hipMemcpyHostToDevice, c->stream));
-        d_dig = ch->d_dig.as<uint8_t>();
-    }
-    const size_t plan_bytes = 4ull * (o_ent + entries);
-    HIP_TRY(c, ch->d_plan.ensure(plan_bytes));
-    HIP_TRY(c, ch->d_out.ensure(32ull * values));
-    HIP_TRY(c, hipMemcpyAsync(ch->d_plan.p, plan, plan_bytes, hipMemcpyHostToDevice, c->stream));
-    const uint32_t* d_plan = ch->d_plan.as<uint32_t>();
-    if (int r = timed_launch(c, 1, [&] {
-            return chains_launch_commit(ch, d_dig, d_plan + o_ent, d_plan, d_plan + o_first, na,
-                                        ch->d_out.as<uint8_t>(), c->stream);
-        }))
-        return r;
-    if (values) HIP_TRY(c, hipMemcpyAsync(values_out, ch->d_out.p, 32ull * values, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // ch->plan and the caller's table feed async copies
-    *n_values_out = values;
-    return MIRSHA_OK;
-}
-}  // namespace
-
-int mirsha_chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, uint32_t n_digests,
-                         const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops, uint8_t* values_out,
-                         uint32_t* n_values_out) {
-    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
-    return chains_commit(c, ch, digests, false, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
-}
-
-int mirsha_chains_commit_device(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* d_digests, uint32_t n_digests,
-                                const uint32_t* op_chain, const uint32_t* op_digest, uint32_t n_ops,
-                                uint8_t* values_out, uint32_t* n_values_out) {
-    if (int rc = chains_hasher_match(c, ch, __func__)) return rc;
-    return chains_commit(c, ch, d_digests, true, n_digests, op_chain, op_digest, n_ops, values_out, n_values_out);
 }
 
 int mirsha_ctx_host_profile(const mirsha_ctx* c, double* ms_out, int n) {

@@ -2,7 +2,7 @@
 // the C-ABI (include/mirsha.h); not part of the ABI.
 //
 //   mirsha_api.hip      contexts, timing, device-pointer API, synthetic
-//                       streams, checkpoint chains, clock probe
+//                       streams, clock probe
 //   mirsha_staging.hip  synchronous host calls: staging, pipelined H2D /
 //                       kernels / D2H (mirsha_hash_batch / _slices /
 //                       _requests_then_batches, mirsha_digest_lists) and their
@@ -18,8 +18,9 @@
 //                       mixed hash-and-verify cycles: *_expect, both in one
 //                       ticket: *_expect_dedup)
 //   mirsha_expect.hip   the select kernels of the mixed submissions
-//   mirsha_commit_ring.hip  a cycle's Commits as a ticket of that ring
-//                       (mirsha_chains_commit_submit*) and their segment kernel
+//   mirsha_chains.hip   checkpoint chains: every mirsha_chains_* entry point (a
+//                       cycle's Commits as a ticket of that ring among them)
+//                       and the SHA-256 chain kernels (mirsha_chains.h)
 //   mirsha_order.hip    the kernels of the device-built bucket order
 //                       (mirsha_order.h; queue_bucket_order in mirsha_api.hip)
 //   mirsha_streams.hip  streaming hash states over any bytes (mirsha_streams_*)
@@ -33,7 +34,7 @@
 //   mirsha_sha512.hip   the request and list kernels of the second hasher,
 //                       SHA-512/256 (mirsha_sha512.h; hasher_launch_* below)
 //   mirsha_sha512_chains.hip  its checkpoint-chain kernels
-//                       (mirsha_sha512_chains.h; chains_launch_* below)
+//                       (mirsha_sha512_chains.h; chain_kernels, mirsha_chains.h)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
 // Digests[i] by the request's position), unlike ProcessorWorkPool's
@@ -60,7 +61,6 @@
 #include "mirsha_device.h"
 #include "mirsha_order.h"
 #include "mirsha_sha512.h"
-#include "mirsha_sha512_chains.h"
 
 namespace mirsha {
 // mirsha_expect.hip.  Mixed cycles (mirsha_submit_*_expect): compares the
@@ -81,19 +81,6 @@ hipError_t launch_expect_select_gather(const uint8_t* digests0, const uint8_t* d
                                        const uint32_t* row_of, const uint8_t* expected, const uint64_t* has,
                                        const uint32_t* base, uint32_t n, uint8_t* out, uint64_t* bits,
                                        uint32_t* count, hipStream_t s);
-
-// mirsha_commit_ring.hip.  A cycle's commit programme cut into segments
-// (mirsha_commit_seg_plan's arrays), one lane per segment.  A FIRST segment
-// starts from its chain's state in h_in / pend_in / cnt_in (the chains' own
-// arrays, or a copy of them taken on the stream ahead of the launch), every
-// other one from Hasher(); a LAST segment stores the state it ends in to
-// h / pend / cnt.  Checkpoint values go to 32-byte rows of `out` (16-byte
-// aligned, device or host-visible memory) with plain vector stores.  `prio`:
-// the issue priority (0-3) the waves take at entry.
-hipError_t launch_chains_commit_seg(const uint8_t* digests, const uint32_t* ent, const uint32_t* seg_chain,
-                                    const uint32_t* sfirst, const uint32_t* seg_flags, uint32_t n_seg,
-                                    const uint32_t* h_in, const uint32_t* pend_in, const uint64_t* cnt_in, uint32_t* h,
-                                    uint32_t* pend, uint64_t* cnt, uint8_t* out, uint32_t prio, hipStream_t s);
 }  // namespace mirsha
 
 namespace mirsha_api {
@@ -312,7 +299,7 @@ struct RingOwner {
 struct mirsha_chains {
     int device = 0;
     uint32_t n = 0;
-    int hasher = MIRSHA_HASHER_SHA256;  // fixed at creation: which kernels chains_launch_* queue
+    int hasher = MIRSHA_HASHER_SHA256;  // fixed at creation: its row of chain_kernels (mirsha_chains.h)
     // state: h / pend / cnt of 32n / 32n / 8n bytes (SHA-256), 64n / 96n / 8n (SHA-512/256)
     DevBuf d_h, d_pend, d_cnt;
     DevBuf d_dig, d_pos, d_act, d_afirst, d_which, d_out;  // per call
@@ -456,69 +443,6 @@ inline int chains_hasher_match(mirsha_ctx* c, const mirsha_chains* ch, const cha
     if (!c || !ch || c->hasher == ch->hasher) return MIRSHA_OK;  // (NULL is the call's own MIRSHA_EINVAL)
     return fail(c, MIRSHA_EINVAL, "%s: the chains hash with %s, the context with %s", call, hasher_name(ch->hasher),
                 hasher_name(c->hasher));
-}
-
-// The chains' hasher decides which kernel a chains launch queues, as
-// hasher_launch_* do by the context's; the callers pass what launch_chains_*
-// take and know nothing else about hashers.  What differs between the hashers
-// is the state's word type and size alone.
-inline uint64_t chains_h_bytes(const mirsha_chains* ch) {
-    return (ch->hasher == MIRSHA_HASHER_SHA512_256 ? 64ull : 32ull) * ch->n;
-}
-inline uint64_t chains_pend_bytes(const mirsha_chains* ch) {
-    return (ch->hasher == MIRSHA_HASHER_SHA512_256 ? 96ull : 32ull) * ch->n;
-}
-inline uint64_t chains_cnt_bytes(const mirsha_chains* ch) { return 8ull * ch->n; }
-
-inline hipError_t chains_launch_commit(const mirsha_chains* ch, const uint8_t* digests, const uint32_t* ent,
-                                       const uint32_t* act, const uint32_t* efirst, uint32_t n_active, uint8_t* out,
-                                       hipStream_t s) {
-    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
-        return mirsha::launch_sha512_chains_commit(digests, ent, act, efirst, n_active, ch->d_h.as<uint64_t>(),
-                                                   ch->d_pend.as<uint64_t>(), ch->d_cnt.as<uint64_t>(), out, s);
-    return mirsha::launch_chains_commit(digests, ent, act, efirst, n_active, ch->d_h.as<uint32_t>(),
-                                        ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), out, s);
-}
-// mirsha_chains_absorb's grouped writes.  Under SHA-512/256 they are a commit
-// programme without checkpoints (pos = the entries), run by the commit kernel.
-inline hipError_t chains_launch_absorb(const mirsha_chains* ch, const uint8_t* digests, const uint32_t* pos,
-                                       const uint32_t* act, const uint32_t* afirst, uint32_t n_active, hipStream_t s) {
-    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
-        return mirsha::launch_sha512_chains_commit(digests, pos, act, afirst, n_active, ch->d_h.as<uint64_t>(),
-                                                   ch->d_pend.as<uint64_t>(), ch->d_cnt.as<uint64_t>(), nullptr, s);
-    return mirsha::launch_chains_absorb(digests, pos, act, afirst, n_active, ch->d_h.as<uint32_t>(),
-                                        ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), s);
-}
-inline hipError_t chains_launch_sum(const mirsha_chains* ch, const uint32_t* which, uint32_t k, uint8_t* out,
-                                    hipStream_t s) {
-    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
-        return mirsha::launch_sha512_chains_sum(which, k, ch->d_h.as<uint64_t>(), ch->d_pend.as<uint64_t>(),
-                                                ch->d_cnt.as<uint64_t>(), out, s);
-    return mirsha::launch_chains_sum(which, k, ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(),
-                                     ch->d_cnt.as<uint64_t>(), out, s);
-}
-inline hipError_t chains_launch_reset(const mirsha_chains* ch, const uint32_t* which, uint32_t k, hipStream_t s) {
-    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
-        return mirsha::launch_sha512_chains_reset(which, k, ch->d_h.as<uint64_t>(), ch->d_cnt.as<uint64_t>(), s);
-    return mirsha::launch_chains_reset(which, k, ch->d_h.as<uint32_t>(), ch->d_cnt.as<uint64_t>(), s);
-}
-// state_in[0..3): where FIRST lanes read h / pend / cnt (the chains' arrays or
-// the ticket's snapshot of them).
-inline hipError_t chains_launch_commit_seg(const mirsha_chains* ch, const uint8_t* digests, const uint32_t* ent,
-                                           const uint32_t* seg_chain, const uint32_t* sfirst, const uint32_t* seg_flags,
-                                           uint32_t n_seg, const uint8_t* const* state_in, uint8_t* out, uint32_t prio,
-                                           hipStream_t s) {
-    const uint64_t* cnt_in = reinterpret_cast<const uint64_t*>(state_in[2]);
-    if (ch->hasher == MIRSHA_HASHER_SHA512_256)
-        return mirsha::launch_sha512_chains_commit_seg(
-            digests, ent, seg_chain, sfirst, seg_flags, n_seg, reinterpret_cast<const uint64_t*>(state_in[0]),
-            reinterpret_cast<const uint64_t*>(state_in[1]), cnt_in, ch->d_h.as<uint64_t>(), ch->d_pend.as<uint64_t>(),
-            ch->d_cnt.as<uint64_t>(), out, prio, s);
-    return mirsha::launch_chains_commit_seg(digests, ent, seg_chain, sfirst, seg_flags, n_seg,
-                                            reinterpret_cast<const uint32_t*>(state_in[0]),
-                                            reinterpret_cast<const uint32_t*>(state_in[1]), cnt_in,
-                                            ch->d_h.as<uint32_t>(), ch->d_pend.as<uint32_t>(), ch->d_cnt.as<uint64_t>(),
-                                            out, prio, s);
 }
 
 int use_device(mirsha_ctx* c);
@@ -783,14 +707,6 @@ int seg_submit(mirsha_ctx* c, const SegTicket& t, Clock::time_point t0, Fill fil
     ring_publish(c, sl, queued, ph, ticket_out);
     return MIRSHA_OK;
 }
-
-// ---- mirsha_api.hip: what mirsha_chains_commit and mirsha_chains_commit_submit
-// share of their checks.  commit_args: the argument checks of a call with ops.
-// commit_plan_failed: the message of a plan's refusal (rc, bad op).
-int commit_args(mirsha_ctx* c, const mirsha_chains* ch, const uint8_t* digests, bool on_device, uint32_t n_digests,
-                const uint32_t* op_chain, const uint32_t* op_digest);
-int commit_plan_failed(mirsha_ctx* c, int rc, uint32_t bad, const mirsha_chains* ch, uint32_t n_digests,
-                       const uint32_t* op_chain, const uint32_t* op_digest);
 
 // ---- mirsha_streams_ring.hip: one preparation of a stream programme (n_ops > 0)
 // for mirsha_streams_run and mirsha_streams_submit.  streams_prepare: every

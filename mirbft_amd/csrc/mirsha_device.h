@@ -1,8 +1,8 @@
 // mirsha_device.h — what the .hip units share beyond the compression itself
 // (sha256_device.h): the one launch path, the issue priority of the segment
-// kernels, the digest-list primitives of the dependent-pass kernels and the
-// step of a commit programme.  HIP only:
-// mirsha_host.cpp (plain C++) never includes it.
+// kernels, the wave-wide max / min, the digest store and the digest-list
+// primitives of the dependent-pass kernels.  HIP only: mirsha_host.cpp (plain
+// C++) never includes it.
 #pragma once
 #include <hip/hip_ext.h>
 
@@ -30,8 +30,7 @@ void launch_k(void (*k)(P...), dim3 grid, dim3 block, uint32_t shmem, hipStream_
 
 // ---- issue priority -------------------------------------------------------
 // The wave's issue priority, once at entry of the two segment kernels
-// (chains_commit_seg_kernel, mirsha_commit_ring.hip; streams_seg_kernel,
-// mirsha_streams_ring.hip).  The priority is wave-uniform; readfirstlane keeps
+// (mirsha_chains.hip, mirsha_streams_ring.hip).  The priority is wave-uniform; readfirstlane keeps
 // the branches scalar, so exactly one s_setprio executes (s_setprio ignores
 // exec: fixed_prio, mirsha_kernels.hip).
 __device__ __forceinline__ void seg_prio(uint32_t p) {
@@ -40,6 +39,40 @@ __device__ __forceinline__ void seg_prio(uint32_t p) {
     else if (p == 2u) __builtin_amdgcn_s_setprio(2);
     else if (p == 1u) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
+}
+
+// ---- wave-wide reductions ------------------------------------------------
+// Wave-wide max / min, wave-uniform result (an SGPR).  DPP inside each 16-lane
+// row (quad_perm xor 1 / xor 2, row_ror 4 / 8: four VALU ops, no LDS), then
+// the four row results by v_readlane and a scalar reduction.  Called with all
+// 64 lanes active (every call site is at a kernel's top, before divergence);
+// a DPP source outside the row keeps the lane's own value.
+// (The DPP moves' "old" operand is the op's identity, so hipcc folds each
+// move into the max / min itself: v_max_u32_dpp, one VALU per step.)
+template <bool kMax>
+__device__ __forceinline__ uint32_t wave_reduce(uint32_t v) {
+    auto op = [](uint32_t a, uint32_t b) { return kMax ? (a > b ? a : b) : (a < b ? a : b); };
+    constexpr int id = kMax ? 0 : -1;
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0x124, 0xF, 0xF, false));  // row_ror:4
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0x128, 0xF, 0xF, false));  // row_ror:8
+    const uint32_t r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
+    const uint32_t r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
+    return op(op(r0, r1), op(r2, r3));
+}
+__device__ __forceinline__ uint32_t wave_max(uint32_t v) { return wave_reduce<true>(v); }
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) { return wave_reduce<false>(v); }
+
+// ---- digests ----------------------------------------------------------------
+// Row `msg` of `out` (16-byte aligned): two plain 128-bit vector stores of the
+// byte-swapped state words.
+__device__ __forceinline__ void store_digest(uint8_t* out, uint32_t msg, const uint32_t st[8]) {
+    uint4* d = reinterpret_cast<uint4*>(out + 32ull * msg);
+    d[0] = make_uint4(__builtin_bswap32(st[0]), __builtin_bswap32(st[1]), __builtin_bswap32(st[2]),
+                      __builtin_bswap32(st[3]));
+    d[1] = make_uint4(__builtin_bswap32(st[4]), __builtin_bswap32(st[5]), __builtin_bswap32(st[6]),
+                      __builtin_bswap32(st[7]));
 }
 
 // ---- digest lists ---------------------------------------------------------
@@ -90,66 +123,6 @@ __device__ __forceinline__ void load_digest(__amdgpu_buffer_rsrc_t rsrc, uint32_
     const auto b = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + 16u, 0, 0);
     x0 = make_uint4(a[0], a[1], a[2], a[3]);
     x1 = make_uint4(b[0], b[1], b[2], b[3]);
-}
-
-// ---- one step of a commit programme ---------------------------------------
-// chains_commit_kernel (mirsha_kernels.hip) and chains_commit_seg_kernel
-// (mirsha_commit_ring.hip) walk a lane's programme in these steps.  A step is
-// at most one compression: two whole digests (the first may be the digest
-// pending from earlier writes), or the final padded block of a checkpoint
-// (pending digest, if any, 0x80, bit length: always one block), or a lone
-// last write that becomes the pending digest without a compression.
-struct CommitStep {
-    uint4 a0, a1, b0, b1;  // raw rows of the two halves (zeros where the step loads none)
-    uint64_t bits;         // checkpoint: the message's bit length
-    uint32_t row;          // checkpoint: output row
-    bool use_pend;         // first half = the pending digest
-    bool have_a;           // checkpoint: a first half precedes the 0x80
-    bool write, cp;        // compress two digests / the final block (neither: nothing to hash)
-    bool keep;             // a lone last write: the first half becomes the pending digest
-};
-
-// Plans step t of a lane at entry e (x0 = ent[e], xn = ent[e + 1], each
-// loaded only below `end`), requests its digest rows, moves e and the digest
-// count n past it and loads the entries of step t + 1.  Which entries a step
-// consumes depends on the entry kinds and the parity only, never on a hash
-// value, so this walk runs one step ahead of the hashing.  Every load is
-// guarded by the lane's own range: past `end` the index would run into the
-// next lane's entries or beyond the array (the note on pos in
-// chains_absorb_kernel).
-__device__ __forceinline__ CommitStep commit_fetch(const uint8_t* __restrict__ digests,
-                                                   const uint32_t* __restrict__ ent, uint32_t end, uint32_t& e,
-                                                   uint64_t& n, uint32_t& x0, uint32_t& xn) {
-    CommitStep s;
-    const bool live = e < end;
-    const bool odd = (n & 1u) != 0u;
-    const bool take0 = live && !odd && !(x0 & kCommitEntryCheckpoint);  // first half from the table
-    const uint32_t e1 = e + (take0 ? 1u : 0u);
-    const bool live1 = live && e1 < end;  // odd && live: e1 == e, so live1
-    const uint32_t x1 = take0 ? xn : x0;
-    s.write = live1 && !(x1 & kCommitEntryCheckpoint);
-    s.cp = live1 && (x1 & kCommitEntryCheckpoint) != 0u;
-    s.use_pend = odd && live1;
-    s.have_a = odd || take0;
-    s.keep = take0 && !live1;
-    s.row = x1 & ~kCommitEntryCheckpoint;
-    s.bits = (n + (take0 ? 1u : 0u)) * 256u;
-    s.a0 = s.a1 = s.b0 = s.b1 = make_uint4(0u, 0u, 0u, 0u);
-    if (take0) {
-        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x0);
-        s.a0 = d[0];
-        s.a1 = d[1];
-    }
-    if (s.write) {
-        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * x1);
-        s.b0 = d[0];
-        s.b1 = d[1];
-    }
-    n = s.cp ? 0u : n + (take0 ? 1u : 0u) + (s.write ? 1u : 0u);
-    e = e1 + (live1 ? 1u : 0u);
-    x0 = e < end ? ent[e] : 0u;
-    xn = e + 1u < end ? ent[e + 1u] : 0u;  // e <= end <= 2^31: no wrap
-    return s;
 }
 
 }  // namespace mirsha

@@ -209,22 +209,6 @@ hipError_t launch_fused_paced(const FusedArgs& a, uint32_t grid, uint32_t pace, 
 // Placement probe of the fused launch's block shape: *broken |= 1 when some
 // block's 4P waves are not dealt P per SIMD (test != 0: report broken).
 hipError_t launch_placement_probe(uint32_t grid, uint32_t pace, uint32_t* broken, uint32_t test, hipStream_t s);
-// Streaming checkpoint chains (state: midstate h[8], pending digest words
-// pend[8], digest count cnt per chain), see mirsha_kernels.hip.
-hipError_t launch_chains_absorb(const uint8_t* digests, const uint32_t* pos, const uint32_t* act, const uint32_t* afirst,
-                                uint32_t n_active, uint32_t* h, uint32_t* pend, uint64_t* cnt, hipStream_t s);
-hipError_t launch_chains_sum(const uint32_t* which, uint32_t k, const uint32_t* h, const uint32_t* pend,
-                             const uint64_t* cnt, uint8_t* out, hipStream_t s);
-hipError_t launch_chains_reset(const uint32_t* which, uint32_t k, uint32_t* h, uint64_t* cnt, hipStream_t s);
-// A cycle's commit programme over those states in one launch
-// (mirsha_commit_plan's arrays): lane k runs entries ent[efirst[k] ..
-// efirst[k+1]) on chain act[k]; an entry is a row of `digests` (16-byte
-// aligned) to write, or kCommitEntryCheckpoint | the row of `out` that gets
-// Sum() before the state restarts.
-constexpr uint32_t kCommitEntryCheckpoint = 0x80000000u;
-hipError_t launch_chains_commit(const uint8_t* digests, const uint32_t* ent, const uint32_t* act,
-                                const uint32_t* efirst, uint32_t n_active, uint32_t* h, uint32_t* pend, uint64_t* cnt,
-                                uint8_t* out, hipStream_t s);
 // Mismatch bitmap of n 32-byte digests against n expected ones (both 16-byte
 // aligned): bit i & 63 of bits[i >> 6] = digest i differs; every word of the
 // ceil(n / 64)-word bitmap is written; *count += mismatches (the caller

@@ -26,28 +26,6 @@
 
 namespace mirsha {
 
-// Wave-wide max / min, wave-uniform result (an SGPR).  DPP inside each 16-lane
-// row (quad_perm xor 1 / xor 2, row_ror 4 / 8: four VALU ops, no LDS), then
-// the four row results by v_readlane and a scalar reduction.  Called with all
-// 64 lanes active (every call site is at a kernel's top, before divergence);
-// a DPP source outside the row keeps the lane's own value.
-// (The DPP moves' "old" operand is the op's identity, so hipcc folds each
-// move into the max / min itself: v_max_u32_dpp, one VALU per step.)
-template <bool kMax>
-__device__ __forceinline__ uint32_t wave_reduce(uint32_t v) {
-    auto op = [](uint32_t a, uint32_t b) { return kMax ? (a > b ? a : b) : (a < b ? a : b); };
-    constexpr int id = kMax ? 0 : -1;
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0x124, 0xF, 0xF, false));  // row_ror:4
-    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(id, (int)v, 0x128, 0xF, 0xF, false));  // row_ror:8
-    const uint32_t r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const uint32_t r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    return op(op(r0, r1), op(r2, r3));
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) { return wave_reduce<true>(v); }
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) { return wave_reduce<false>(v); }
-
 // Raw 20 bytes (5 dwords) covering the 16-byte chunk q of block blk of a
 // message at arena offset o: aligned down to 4 bytes, the byte shift is
 // resolved later by v_perm.  Inactive chunks read at an out-of-range offset,
@@ -165,14 +143,6 @@ __device__ __forceinline__ void finish_chunk(const RawChunk& c, uint32_t p, uint
 // Swizzled 16-byte slot of (message m, quarter q) inside a wave's 256-slot tile.
 __device__ __forceinline__ uint32_t lds_slot(uint32_t m, uint32_t q) {
     return m * 4u + (q ^ ((m >> 2) & 3u));
-}
-
-__device__ __forceinline__ void store_digest(uint8_t* out, uint32_t msg, const uint32_t st[8]) {
-    uint4* d = reinterpret_cast<uint4*>(out + 32ull * msg);
-    d[0] = make_uint4(__builtin_bswap32(st[0]), __builtin_bswap32(st[1]), __builtin_bswap32(st[2]),
-                      __builtin_bswap32(st[3]));
-    d[1] = make_uint4(__builtin_bswap32(st[4]), __builtin_bswap32(st[5]), __builtin_bswap32(st[6]),
-                      __builtin_bswap32(st[7]));
 }
 
 __device__ __forceinline__ void store_digest_buf(__amdgpu_buffer_rsrc_t ors, uint32_t msg, const uint32_t st[8]) {
@@ -2055,227 +2025,6 @@ hipError_t launch_placement_probe(uint32_t grid, uint32_t pace, uint32_t* broken
 hipError_t launch_mixed_lengths(uint64_t seed, uint64_t first, uint64_t count, uint32_t* len, hipStream_t s) {
     if (count == 0) return hipSuccess;
     launch_k(mixed_lengths_kernel, (unsigned)((count + 255u) / 256u), 256, 0, s, seed, first, count, len);
-    return hipGetLastError();
-}
-
-// ---- streaming checkpoint chains (testengine NodeState.ActiveHash) ---------
-// Running SHA-256 states, one per application node: the checkpoint value of
-// testengine/recorder.go:213-256 is Sum() of a hash that every committed
-// request digest is written into (ActiveHash.Write, :223), reset at each
-// checkpoint (Set, :187).  State per chain: midstate h[8], the pending
-// digest of an odd count (its 8 big-endian words) and the digest count.
-// Writes are 32-byte digests, so a block is always two whole digests.
-__device__ __forceinline__ void load_digest_words(const uint8_t* __restrict__ digests, uint32_t p, bool live,
-                                                  uint32_t w[8]) {
-    if (live) {
-        const uint4* d = reinterpret_cast<const uint4*>(digests + 32ull * p);
-        const uint4 a = d[0], b = d[1];
-        be_words(a, w);
-        be_words(b, w + 4);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 8; i++) w[i] = 0u;
-    }
-}
-
-// One lane per chain with new digests pos[afirst[k] .. afirst[k+1]) (in write
-// order).  With `odd` = a digest pending from earlier writes, the lane
-// completes (odd + m) / 2 blocks: block t = digest q ‖ digest q+1 with
-// q = 2t - odd (q = -1: the pending digest).
-__global__ __launch_bounds__(kBlockThreads) void chains_absorb_kernel(
-    const uint8_t* __restrict__ digests, const uint32_t* __restrict__ pos, const uint32_t* __restrict__ act,
-    const uint32_t* __restrict__ afirst, uint32_t n_active, uint32_t* __restrict__ h, uint32_t* __restrict__ pend,
-    uint64_t* __restrict__ cnt) {
-    const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
-    const bool valid = k < n_active;
-    const uint32_t c = valid ? act[k] : 0u;
-    const uint32_t e0 = valid ? afirst[k] : 0u;
-    const uint32_t m = valid ? afirst[k + 1] - e0 : 0u;
-    uint32_t st[8], pw[8];
-    uint64_t n = 0;
-    if (valid) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            st[i] = h[8ull * c + i];
-            pw[i] = pend[8ull * c + i];
-        }
-        n = cnt[c];
-    }
-    const uint32_t odd = (uint32_t)(n & 1u);
-    const uint32_t blocks = (odd + m) / 2u;
-    const uint32_t steps = wave_max(blocks);
-    for (uint32_t t = 0; t < steps; t++) {
-        const bool live = t < blocks;
-        const int32_t q = (int32_t)(2u * t) - (int32_t)odd;
-        uint32_t w[16];
-        if (q < 0) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) w[i] = pw[i];
-        } else {
-            // Guarded like the second load below: past this lane's own block
-            // count the index would run beyond its range in pos.
-            load_digest_words(digests, live ? pos[e0 + (uint32_t)q] : 0u, live, w);
-        }
-        load_digest_words(digests, live ? pos[e0 + (uint32_t)(q + 1)] : 0u, live, w + 8);
-        if (live) compress_asm_lat(st, w);
-    }
-    if (valid) {
-        if ((odd + m) & 1u) {
-            if (m) load_digest_words(digests, pos[e0 + m - 1u], true, pw);  // else the old pending stays
-        }
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            h[8ull * c + i] = st[i];
-            pend[8ull * c + i] = pw[i];
-        }
-        cnt[c] = n + m;
-    }
-}
-
-// Sum(nil) of chains which[0..k): the final padded block (pending digest, if
-// any, then 0x80 and the 64-bit bit length) from a copy of the midstate.
-__global__ __launch_bounds__(kBlockThreads) void chains_sum_kernel(const uint32_t* __restrict__ which, uint32_t k_n,
-                                                                   const uint32_t* __restrict__ h,
-                                                                   const uint32_t* __restrict__ pend,
-                                                                   const uint64_t* __restrict__ cnt,
-                                                                   uint8_t* __restrict__ out) {
-    const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
-    const bool valid = k < k_n;
-    const uint32_t c = valid ? which[k] : 0u;
-    uint32_t st[8], w[16];
-    const uint64_t n = valid ? cnt[c] : 0u;
-    const bool odd = (n & 1u) != 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        st[i] = valid ? h[8ull * c + i] : 0u;
-        w[i] = odd ? pend[8ull * c + i] : 0u;
-        w[8 + i] = 0u;
-    }
-    w[odd ? 8 : 0] = 0x80000000u;
-    const uint64_t bits = n * 256u;
-    w[14] = (uint32_t)(bits >> 32);
-    w[15] = (uint32_t)bits;
-    compress_asm_lat(st, w);
-    if (valid) store_digest(out, k, st);
-}
-
-__global__ __launch_bounds__(kBlockThreads) void chains_reset_kernel(const uint32_t* __restrict__ which, uint32_t k_n,
-                                                                     uint32_t* __restrict__ h,
-                                                                     uint64_t* __restrict__ cnt) {
-    const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
-    if (k >= k_n) return;
-    const uint32_t c = which[k];
-#pragma unroll
-    for (int i = 0; i < 8; i++) h[8ull * c + i] = kH0[i];
-    cnt[c] = 0u;
-}
-
-// ---- a cycle's Commits in one launch (processor.go:145-168) -----------------
-// The commit loop of Processor.Process applies every committed batch to the
-// application log and takes the log's value at each checkpoint; with the
-// testengine's log (NodeState.Commit, testengine/recorder.go:213-256) that is
-// a programme of Write(digest) and Sum-then-fresh-hasher per node.  One lane
-// per chain that has entries this cycle (mirsha_commit_plan): entries
-// ent[efirst[k] .. efirst[k+1]) in op order, null writes already removed.  An
-// entry below kCommitEntryCheckpoint is a row of the shared digest table to
-// write; otherwise its low 31 bits are the output row of a checkpoint.
-//
-// A step is at most one compression per lane: two whole digests (the first
-// may be the digest pending from earlier writes), or the final padded block
-// of a checkpoint (pending digest, if any, 0x80, bit length: always one
-// block), after which the lane's state is Hasher() again.  A lone last write
-// becomes the pending digest without a compression.  The state left behind is
-// chains_absorb_kernel's, so the calls mix freely on one mirsha_chains.
-//
-// Which entries a step consumes depends on the entry kinds and the parity
-// only, never on a hash value, so the lane's walk over its programme
-// (commit_fetch, mirsha_device.h) runs one step ahead of the hashing: the next step's entries
-// were loaded a step earlier, its digest rows are requested before this
-// step's compression and first touched (byte swap) after it.  A lone lane
-// then pays max(compression, one load) per step, not their sum.
-__global__ __launch_bounds__(kBlockThreads) void chains_commit_kernel(
-    const uint8_t* __restrict__ digests, const uint32_t* __restrict__ ent, const uint32_t* __restrict__ act,
-    const uint32_t* __restrict__ efirst, uint32_t n_active, uint32_t* __restrict__ h, uint32_t* __restrict__ pend,
-    uint64_t* __restrict__ cnt, uint8_t* __restrict__ out) {
-    const uint32_t k = blockIdx.x * kBlockThreads + threadIdx.x;
-    const bool valid = k < n_active;
-    const uint32_t c = valid ? act[k] : 0u;
-    uint32_t e = valid ? efirst[k] : 0u;
-    const uint32_t end = valid ? efirst[k + 1] : 0u;
-    uint32_t st[8], pw[8];
-    uint64_t n = 0;
-    if (valid) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            st[i] = h[8ull * c + i];
-            pw[i] = pend[8ull * c + i];
-        }
-        n = cnt[c];
-    }
-    uint32_t x0 = e < end ? ent[e] : 0u;
-    uint32_t xn = e + 1u < end ? ent[e + 1u] : 0u;
-    CommitStep s = commit_fetch(digests, ent, end, e, n, x0, xn);
-    // Wave-uniform: a lane whose step does nothing has reached its end (only a
-    // programme's last step can be without a compression).
-    while (__ballot(s.write || s.cp || s.keep) != 0ull) {
-        const CommitStep nx = commit_fetch(digests, ent, end, e, n, x0, xn);
-        uint32_t w[16];
-        be_words(s.a0, w); be_words(s.a1, w + 4); be_words(s.b0, w + 8); be_words(s.b1, w + 12);
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            if (s.use_pend) w[i] = pw[i];
-            if (s.keep) pw[i] = w[i];
-        }
-        if (s.cp) {
-            if (s.have_a) w[8] = 0x80000000u; else w[0] = 0x80000000u;
-            w[14] = (uint32_t)(s.bits >> 32);
-            w[15] = (uint32_t)s.bits;
-        }
-        if (s.write || s.cp) compress_asm_lat(st, w);
-        if (s.cp) {
-            store_digest(out, s.row, st);
-#pragma unroll
-            for (int i = 0; i < 8; i++) st[i] = kH0[i];
-        }
-        s = nx;
-    }
-    if (valid) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-            h[8ull * c + i] = st[i];
-            pend[8ull * c + i] = pw[i];
-        }
-        cnt[c] = n;
-    }
-}
-
-hipError_t launch_chains_commit(const uint8_t* digests, const uint32_t* ent, const uint32_t* act,
-                                const uint32_t* efirst, uint32_t n_active, uint32_t* h, uint32_t* pend, uint64_t* cnt,
-                                uint8_t* out, hipStream_t s) {
-    if (n_active == 0) return hipSuccess;
-    launch_k(chains_commit_kernel, (n_active + kBlockThreads - 1u) / kBlockThreads, kBlockThreads, 0, s, digests, ent,
-             act, efirst, n_active, h, pend, cnt, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_chains_absorb(const uint8_t* digests, const uint32_t* pos, const uint32_t* act, const uint32_t* afirst,
-                                uint32_t n_active, uint32_t* h, uint32_t* pend, uint64_t* cnt, hipStream_t s) {
-    if (n_active == 0) return hipSuccess;
-    launch_k(chains_absorb_kernel, (n_active + kBlockThreads - 1u) / kBlockThreads, kBlockThreads, 0, s, 
-        digests, pos, act, afirst, n_active, h, pend, cnt);
-    return hipGetLastError();
-}
-
-hipError_t launch_chains_sum(const uint32_t* which, uint32_t k, const uint32_t* h, const uint32_t* pend,
-                             const uint64_t* cnt, uint8_t* out, hipStream_t s) {
-    if (k == 0) return hipSuccess;
-    launch_k(chains_sum_kernel, (k + kBlockThreads - 1u) / kBlockThreads, kBlockThreads, 0, s, which, k, h, pend, cnt, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_chains_reset(const uint32_t* which, uint32_t k, uint32_t* h, uint64_t* cnt, hipStream_t s) {
-    if (k == 0) return hipSuccess;
-    launch_k(chains_reset_kernel, (k + kBlockThreads - 1u) / kBlockThreads, kBlockThreads, 0, s, which, k, h, cnt);
     return hipGetLastError();
 }
 

@@ -17,7 +17,10 @@
 // waiting; lanes depend on each other only through the walk's ballot.
 #include "mirsha_sha512_chains.h"
 
+#include <cstring>
+
 #include "../../include/mirsha.h"
+#include "mirsha_chains.h"
 #include "mirsha_device.h"
 #include "sha512_chain.h"
 
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(kChainWave) void sha512_chains_reset_kernel(const u
 }
 
 // One lane per segment of a cycle's commit programme (mirsha_commit_seg_plan),
-// as chains_commit_seg_kernel (mirsha_commit_ring.hip): a lane that is not its
+// as chains_commit_seg_kernel (mirsha_chains.hip): a lane that is not its
 // chain's FIRST segment starts from Hasher(), only a LAST one stores the state
 // it ends in, and the wave takes its issue priority once at entry.  FIRST lanes
 // read h_in / pend_in / cnt_in: the chains' own arrays, or the copy of them the
@@ -210,42 +213,44 @@ __global__ __launch_bounds__(kChainWave) void sha512_chains_commit_seg_kernel(
     if (flags & MIRSHA_COMMIT_SEG_LAST) chain_state_store(h, pend, cnt, c, st, pw, n);
 }
 
-void sha512_chains_h0(uint64_t h0[8]) {
-    for (int i = 0; i < 8; i++) h0[i] = sha512::kH0[i];
-}
+void sha512_chains_h0(void* h) { memcpy(h, sha512::kH0, sizeof(sha512::kH0)); }
+
+namespace {
+uint64_t* u64(void* p) { return static_cast<uint64_t*>(p); }
+const uint64_t* u64(const void* p) { return static_cast<const uint64_t*>(p); }
+}  // namespace
 
 hipError_t launch_sha512_chains_commit(const uint8_t* digests, const uint32_t* ent, const uint32_t* act,
-                                       const uint32_t* efirst, uint32_t n_active, uint64_t* h, uint64_t* pend,
+                                       const uint32_t* efirst, uint32_t n_active, void* h, void* pend,
                                        uint64_t* cnt, uint8_t* out, hipStream_t s) {
     if (n_active == 0) return hipSuccess;
     launch_k(sha512_chains_commit_kernel, (n_active + kChainWave - 1u) / kChainWave, kChainWave, 0, s, digests, ent, act,
-             efirst, n_active, h, pend, cnt, reinterpret_cast<uint4*>(out));
+             efirst, n_active, u64(h), u64(pend), cnt, reinterpret_cast<uint4*>(out));
     return hipGetLastError();
 }
 
-hipError_t launch_sha512_chains_sum(const uint32_t* which, uint32_t k, const uint64_t* h, const uint64_t* pend,
+hipError_t launch_sha512_chains_sum(const uint32_t* which, uint32_t k, const void* h, const void* pend,
                                     const uint64_t* cnt, uint8_t* out, hipStream_t s) {
     if (k == 0) return hipSuccess;
-    launch_k(sha512_chains_sum_kernel, (k + kChainWave - 1u) / kChainWave, kChainWave, 0, s, which, k, h, pend, cnt,
-             reinterpret_cast<uint4*>(out));
+    launch_k(sha512_chains_sum_kernel, (k + kChainWave - 1u) / kChainWave, kChainWave, 0, s, which, k, u64(h), u64(pend),
+             cnt, reinterpret_cast<uint4*>(out));
     return hipGetLastError();
 }
 
-hipError_t launch_sha512_chains_reset(const uint32_t* which, uint32_t k, uint64_t* h, uint64_t* cnt, hipStream_t s) {
+hipError_t launch_sha512_chains_reset(const uint32_t* which, uint32_t k, void* h, uint64_t* cnt, hipStream_t s) {
     if (k == 0) return hipSuccess;
-    launch_k(sha512_chains_reset_kernel, (k + kChainWave - 1u) / kChainWave, kChainWave, 0, s, which, k, h, cnt);
+    launch_k(sha512_chains_reset_kernel, (k + kChainWave - 1u) / kChainWave, kChainWave, 0, s, which, k, u64(h), cnt);
     return hipGetLastError();
 }
 
 hipError_t launch_sha512_chains_commit_seg(const uint8_t* digests, const uint32_t* ent, const uint32_t* seg_chain,
                                            const uint32_t* sfirst, const uint32_t* seg_flags, uint32_t n_seg,
-                                           const uint64_t* h_in, const uint64_t* pend_in, const uint64_t* cnt_in,
-                                           uint64_t* h, uint64_t* pend, uint64_t* cnt, uint8_t* out, uint32_t prio,
-                                           hipStream_t s) {
+                                           const void* h_in, const void* pend_in, const uint64_t* cnt_in, void* h,
+                                           void* pend, uint64_t* cnt, uint8_t* out, uint32_t prio, hipStream_t s) {
     if (n_seg == 0) return hipSuccess;
     launch_k(sha512_chains_commit_seg_kernel, (n_seg + kChainWave - 1u) / kChainWave, kChainWave, 0, s, digests, ent,
-             seg_chain, sfirst, seg_flags, n_seg, h_in, pend_in, cnt_in, h, pend, cnt, reinterpret_cast<uint4*>(out),
-             prio);
+             seg_chain, sfirst, seg_flags, n_seg, u64(h_in), u64(pend_in), cnt_in, u64(h), u64(pend), cnt,
+             reinterpret_cast<uint4*>(out), prio);
     return hipGetLastError();
 }
 

@@ -117,7 +117,7 @@ struct StreamArgs {
 // step guards the row's store.  A lane past its end idles (op 4) until the
 // wave's last lane is done.  An entry's record is loaded unguarded at an index
 // clamped into the lane's own range (the note on commit_fetch,
-// mirsha_device.h), or at 0 for an idle lane: a launch has at least one entry.
+// mirsha_chains.hip), or at 0 for an idle lane: a launch has at least one entry.
 // The walk runs one step ahead of the hashing, as commit_fetch: which bytes a
 // step takes depends on the entries and the byte count only, never on a hash
 // value, so the next step's window (and the entry behind the next) is

@@ -4,7 +4,7 @@
 // (`type Hasher func() hash.Hash`, processor.go:21) and an application log
 // that writes more than whole digests (Log.Apply / Log.Snap,
 // processor.go:28-31).  A translation unit of its own, as
-// mirsha_commit_ring.hip: the hashing kernels keep their code object.
+// mirsha_chains.hip: the hashing kernels keep their code object.
 #include "mirsha_ctx.h"
 #include "mirsha_streams.h"
 

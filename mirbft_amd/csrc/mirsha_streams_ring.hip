@@ -1,7 +1,7 @@
 // mirsha_streams_ring.hip — a stream programme on the asynchronous ring
 // (mirsha_streams_submit / _submit_device, include/mirsha.h): the ring form of
-// mirsha_streams_run, as mirsha_commit_ring.hip is the ring form of
-// mirsha_chains_commit.  With it an application log that writes any bytes
+// mirsha_streams_run, as mirsha_chains_commit_submit is the ring form of
+// mirsha_chains_commit (mirsha_chains.hip).  With it an application log that writes any bytes
 // (StreamLog) has its commit stage beside the hash stage (commitInParallel,
 // processor.go:447-470).  A translation unit of its own: the hashing kernels
 // keep their code object, and the synchronous mirsha_streams_run keeps its

@@ -1,6 +1,6 @@
 """Resources of the gathering select kernel (CPU: hipcc's resource-usage remarks
-for gfx950, device code only, as tests/test_commit_ring_resources.py does for
-mirsha_commit_ring.hip).  expect_select_gather_kernel is one lane per request
+for gfx950, device code only, as tests/test_chains_resources.py does for
+mirsha_chains.hip).  expect_select_gather_kernel is one lane per request
 with five loads and two stores: scratch, a spill or LDS would mean the
 compiler did not keep the two digest words in registers across the ballot."""
 import os

@@ -54,6 +54,12 @@ def test_no_scratch_or_spills(resources):
     assert not bad, f"kernels spilling to scratch: {bad}"
 
 
+def test_the_unit_holds_no_chain_kernel(resources):
+    """The checkpoint-chain kernels stay in their own code object
+    (mirsha_chains.hip, tests/test_chains_resources.py)."""
+    assert not [k for k in resources if "chains_" in k], sorted(resources)
+
+
 @pytest.mark.parametrize("name,occ", sorted(OCCUPANCY.items()))
 def test_occupancy(resources, name, occ):
     hits = {k: v for k, v in resources.items() if name in k}

@@ -1,5 +1,5 @@
 """Resources of the order kernels (CPU: hipcc's resource-usage remarks for
-gfx950, device code only, as tests/test_commit_ring_resources.py does for the
+gfx950, device code only, as tests/test_chains_resources.py does for the
 commits' segment kernel).  The count and scatter kernels are one wave per
 workgroup walking its chunk; a spill to scratch would put memory round trips
 into the scatter's match loop."""
