@@ -619,15 +619,20 @@ int mirsha_ctx_order_mode(const mirsha_ctx* ctx);
  * MIRSHA_EINVAL and a message that names the call and both hashers when it
  * does not (a log that hashes with another function than the requests is a
  * misconfiguration).  A commit ticket keeps the function it was queued with.
+ * The streaming hash states carry a hasher of their own in the same way
+ * (mirsha_streams_create_hasher): mirsha_streams_run / _run_device / _submit /
+ * _submit_device / _export / _import are served when the context's hasher
+ * equals the streams', and refused with MIRSHA_EINVAL and a message that names
+ * the call and both hashers when it does not.  A stream ticket keeps the
+ * function it was queued with.
  * Calls built for SHA-256 only refuse any other hasher at entry with
  * MIRSHA_EINVAL and a message that names the call and the hasher.  Either
  * refusal comes ahead of any other effect (state, ring and tickets stay as
  * they were; there is no silent SHA-256 and no CPU path).  SHA-256 only:
  * mirsha_pipeline_create / _create_mode,
- * mirsha_hash_requests_then_batches_device, mirsha_pipeline_overlap_device,
- * mirsha_streams_run / _run_device / _submit /
- * _submit_device / _export / _import.  The mirsha_multi_* forms own their
- * contexts, which stay SHA-256.
+ * mirsha_hash_requests_then_batches_device, mirsha_pipeline_overlap_device
+ * (there is no SHA-512/256 form of the device plans).  The mirsha_multi_* forms
+ * own their contexts, which stay SHA-256.
  * mirsha_ctx_set_hasher: MIRSHA_EINVAL for a NULL context or an unknown value
  * (processor.go:21,58). */
 #define MIRSHA_HASHER_SHA256 0
@@ -832,6 +837,20 @@ int mirsha_chains_commit_submit_device(mirsha_ctx* ctx, mirsha_chains* chains, c
  * bytes of the unfinished block, and the total byte count (u64, so the padded
  * bit length is 64-bit).  Every stream starts as Hasher().
  *
+ * A hash.Hash is made by the node's Hasher, so a streams object has one, fixed
+ * at creation, as the chains have:
+ *   mirsha_streams_create: SHA-256 streams, whatever the context's hasher.
+ *   mirsha_streams_create_hasher: streams of `hasher` (MIRSHA_HASHER_*; an
+ *     unknown value is MIRSHA_EINVAL).  SHA-512/256 streams keep h as 8 64-bit
+ *     words, the up to 127 bytes of the unfinished 128-byte block and the byte
+ *     count (u64; the padded bit length is 128-bit, FIPS 180-4: above 2^61
+ *     bytes Go's crypto/sha512 leaves its high 64 bits zero, this does not).
+ *   mirsha_streams_hasher: the streams' hasher; MIRSHA_EINVAL for NULL.
+ * The six calls below that run, queue, export or import need a context whose
+ * hasher is the streams' own, else MIRSHA_EINVAL ahead of any other effect
+ * (the states and the ring stay as they were; the same object is served again
+ * once the context is set back).
+ *
  * One call runs ONE programme of n_ops ops in ONE kernel launch (timing id
  * 9), one lane per active stream.  Op i acts on stream op_stream[i]
  * (< n_streams); ops of one stream take effect in op order, streams are
@@ -840,6 +859,8 @@ int mirsha_chains_commit_submit_device(mirsha_ctx* ctx, mirsha_chains* chains, c
  * for every other kind. */
 typedef struct mirsha_streams mirsha_streams;
 int mirsha_streams_create(mirsha_ctx* ctx, uint32_t n_streams, mirsha_streams** out);
+int mirsha_streams_create_hasher(mirsha_ctx* ctx, uint32_t n_streams, int hasher, mirsha_streams** out);
+int mirsha_streams_hasher(const mirsha_streams* streams);
 void mirsha_streams_destroy(mirsha_streams* streams);
 
 #define MIRSHA_STREAM_WRITE 0u     /* Write(arena[op_off[i] .. op_off[i]+op_len[i])) */
@@ -848,8 +869,14 @@ void mirsha_streams_destroy(mirsha_streams* streams);
 #define MIRSHA_STREAM_RESET 3u
 /* At most this many ops a call (a plan entry keeps its kind in 2 bits beside its value row). */
 #define MIRSHA_STREAM_MAX_OPS 0x3FFFFFFFu
-/* Bytes of one exported state (mirsha_streams_export). */
+/* Bytes of one exported state (mirsha_streams_export) of SHA-256 streams, and
+ * of SHA-512/256 streams. */
 #define MIRSHA_STREAM_STATE_BYTES 108u
+#define MIRSHA_STREAM_STATE_BYTES_SHA512 204u
+/* The same by hasher: 108 for MIRSHA_HASHER_SHA256, 204 for
+ * MIRSHA_HASHER_SHA512_256.  Host only, no context, like mirsha_hasher_info;
+ * bytes_out may be NULL.  MIRSHA_EINVAL: an unknown hasher. */
+int mirsha_stream_state_bytes(int hasher, uint32_t* bytes_out);
 
 /* Host-only (no device, no context), with the role mirsha_commit_plan has for
  * the chains: exactly the arrays mirsha_streams_run* sends to the device.
@@ -915,15 +942,21 @@ int mirsha_streams_run_device(mirsha_ctx* ctx, mirsha_streams* streams, const ui
  * "sha\x03", h[0..7] as big-endian u32, the buffered bytes zero-padded to 64,
  * the total length as big-endian u64.  With no Go toolchain at hand this
  * layout is pinned by that description only, not by a round trip through Go.
- * _import sets the states from such rows (fill = length mod 64) and rejects a
- * wrong magic (MIRSHA_EINVAL, the message names the row; nothing is changed).
+ * SHA-512/256 streams: MIRSHA_STREAM_STATE_BYTES_SHA512 (204) bytes each, Go
+ * 1.14's crypto/sha512 MarshalBinary for New512_256: the magic "sha\x06",
+ * h[0..7] as big-endian u64, the buffered bytes zero-padded to 128, the total
+ * length as big-endian u64; pinned by this description only, in the same way.
+ * _import sets the states from such rows (fill = length mod the block size) and
+ * rejects a wrong magic (MIRSHA_EINVAL, the message names the row; nothing is
+ * changed): a "sha\x03" row offered to SHA-512/256 streams is one, and so is a
+ * "sha\x06" row offered to SHA-256 streams.
  * Synchronous; MIRSHA_EINVAL for a stream id >= n_streams.
  *
  * On an object with a stream ticket in flight (mirsha_streams_submit, below)
  * _run*, _export and _import first make the context's stream wait for it.
  *
  * Not built here: mirsha_multi_* forms, the C++ mirror, the Go files,
- * SHA-224. */
+ * SHA-224, SHA-384 / SHA-512 / SHA-512/224. */
 int mirsha_streams_export(mirsha_ctx* ctx, mirsha_streams* streams, const uint32_t* which, uint32_t k, uint8_t* out);
 int mirsha_streams_import(mirsha_ctx* ctx, mirsha_streams* streams, const uint32_t* which, uint32_t k,
                           const uint8_t* in);

@@ -31,6 +31,7 @@ MIRSHA_STREAM_SUM_RESET = 2
 MIRSHA_STREAM_RESET = 3
 MIRSHA_STREAM_MAX_OPS = 0x3FFFFFFF
 MIRSHA_STREAM_STATE_BYTES = 108
+MIRSHA_STREAM_STATE_BYTES_SHA512 = 204
 MIRSHA_STREAM_SEG_FIRST = 1
 MIRSHA_STREAM_SEG_LAST = 2
 MIRSHA_MAX_MESSAGE_BYTES = 0xFFFFFF00
@@ -193,6 +194,9 @@ SIGNATURES = {
         [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, _u32p, _u64p],
     ),
     "mirsha_streams_create": (c_int, [c_void_p, c_uint32, POINTER(c_void_p)]),
+    "mirsha_streams_create_hasher": (c_int, [c_void_p, c_uint32, c_int, POINTER(c_void_p)]),
+    "mirsha_streams_hasher": (c_int, [c_void_p]),
+    "mirsha_stream_state_bytes": (c_int, [c_int, _u32p]),
     "mirsha_streams_destroy": (None, [c_void_p]),
     "mirsha_stream_plan": (
         c_int,

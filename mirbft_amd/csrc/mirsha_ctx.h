@@ -35,6 +35,8 @@
 //                       SHA-512/256 (mirsha_sha512.h; hasher_launch_* below)
 //   mirsha_sha512_chains.hip  its checkpoint-chain kernels
 //                       (mirsha_sha512_chains.h; chain_kernels, mirsha_chains.h)
+//   mirsha_sha512_streams.hip  its stream kernels
+//                       (mirsha_sha512_streams.h; stream_kernels, mirsha_streams.h)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
 // Digests[i] by the request's position), unlike ProcessorWorkPool's
@@ -314,7 +316,9 @@ struct mirsha_chains {
 struct mirsha_streams {
     int device = 0;
     uint32_t n = 0;
-    DevBuf d_state;  // kStreamStateBytes per stream (mirsha_streams.h)
+    int hasher = MIRSHA_HASHER_SHA256;  // fixed at creation: its row of stream_kernels (mirsha_streams.h)
+    uint32_t row_bytes = 0;             // that row's: a stream's row on the device
+    DevBuf d_state;  // row_bytes per stream (mirsha_streams.h, mirsha_sha512_streams.h)
     // mirsha_stream_plan's arrays of the call being run or submitted, and
     // mirsha_stream_seg_plan's of a submission (kept across calls)
     std::vector<uint32_t> act, efirst, kind, len;
@@ -428,7 +432,7 @@ inline hipError_t hasher_launch_lists(const mirsha_ctx* c, const uint8_t* digest
 
 inline const char* hasher_name(int hasher) { return hasher == MIRSHA_HASHER_SHA512_256 ? "sha512_256" : "sha256"; }
 
-// The entry guard of a call that is built for SHA-256 only (plans, streams):
+// The entry guard of a call that is built for SHA-256 only (the device plans):
 // refused under any other hasher, ahead of any other effect.
 inline int sha256_only(mirsha_ctx* c, const char* call) {
     if (!c || c->hasher == MIRSHA_HASHER_SHA256) return MIRSHA_OK;  // (a NULL context is the call's own MIRSHA_EINVAL)
@@ -442,6 +446,14 @@ inline int sha256_only(mirsha_ctx* c, const char* call) {
 inline int chains_hasher_match(mirsha_ctx* c, const mirsha_chains* ch, const char* call) {
     if (!c || !ch || c->hasher == ch->hasher) return MIRSHA_OK;  // (NULL is the call's own MIRSHA_EINVAL)
     return fail(c, MIRSHA_EINVAL, "%s: the chains hash with %s, the context with %s", call, hasher_name(ch->hasher),
+                hasher_name(c->hasher));
+}
+
+// The same for the six stream calls (run, run_device, submit, submit_device,
+// export, import) and the streams' own hasher.
+inline int streams_hasher_match(mirsha_ctx* c, const mirsha_streams* st, const char* call) {
+    if (!c || !st || c->hasher == st->hasher) return MIRSHA_OK;  // (NULL is the call's own MIRSHA_EINVAL)
+    return fail(c, MIRSHA_EINVAL, "%s: the streams hash with %s, the context with %s", call, hasher_name(st->hasher),
                 hasher_name(c->hasher));
 }
 

@@ -57,6 +57,22 @@ hipError_t launch_streams_seg(const uint32_t* arena_words, uint32_t shift, uint3
                               const uint32_t* sfirst, const uint32_t* seg_flags, const uint32_t* ent, uint32_t n_seg,
                               const uint8_t* state_in, uint8_t* state, uint8_t* out, uint32_t prio, hipStream_t s);
 
+// What a hasher's streams are to the host (mirsha_streams.hip): the row's
+// size, the exported state, and the launchers of its two kernels, which follow
+// the contracts of launch_streams / launch_streams_seg above with rows of
+// row_bytes.  The SHA-512/256 row's kernels: mirsha_sha512_streams.h.
+struct StreamKernels {
+    uint32_t row_bytes;     // a stream's row on the device (16-byte multiple)
+    uint32_t export_bytes;  // one exported state (mirsha_stream_state_bytes)
+    uint8_t magic[4];       // its first four bytes
+    void (*row0)(uint8_t* row);                       // Hasher() as a device row
+    void (*pack)(const uint8_t* row, uint8_t* out);   // a device row -> the exported state behind the magic
+    void (*unpack)(const uint8_t* in, uint8_t* row);  // its inverse: every byte of the row is written
+    decltype(&launch_streams) run;
+    decltype(&launch_streams_seg) seg;
+};
+const StreamKernels& stream_kernels(int hasher);
+
 // The bytes of big-endian message word i (block bytes 4 i .. 4 i + 3) that lie
 // at block positions >= x, as a mask; x in [0, 64].
 __device__ __forceinline__ uint32_t bytes_from(uint32_t x, int i) {

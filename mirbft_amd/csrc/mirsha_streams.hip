@@ -6,6 +6,7 @@
 // processor.go:28-31).  A translation unit of its own, as
 // mirsha_chains.hip: the hashing kernels keep their code object.
 #include "mirsha_ctx.h"
+#include "mirsha_sha512_streams.h"
 #include "mirsha_streams.h"
 
 namespace mirsha {
@@ -39,15 +40,7 @@ hipError_t launch_streams(const uint32_t* arena_words, uint32_t shift, uint32_t 
     return hipGetLastError();
 }
 
-}  // namespace mirsha
-
-namespace mirsha_api {
-
 namespace {
-
-constexpr uint32_t kStateBytes = MIRSHA_STREAM_STATE_BYTES;
-constexpr uint32_t kRowWords = mirsha::kStreamStateBytes / 4u;  // a stream's row on the device
-const uint8_t kStateMagic[4] = {'s', 'h', 'a', 3};
 
 inline void put_be32(uint8_t* p, uint32_t v) {
     p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v;
@@ -55,6 +48,81 @@ inline void put_be32(uint8_t* p, uint32_t v) {
 inline uint32_t get_be32(const uint8_t* p) {
     return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3];
 }
+
+// The SHA-256 row of stream_kernels.  A device row as u32 words:
+// [h 8 | block 16 | count lo, hi | 0, 0] (mirsha_streams.h); an exported state:
+// the magic, h as big-endian u32, the buffered bytes zero-padded to 64, the
+// length as big-endian u64.
+void stream_row0(uint8_t* row) {  // Hasher(): H0, nothing buffered, count 0
+    memset(row, 0, kStreamStateBytes);
+    memcpy(row, kH0, sizeof(kH0));
+}
+void stream_pack(const uint8_t* row, uint8_t* out) {
+    uint32_t r[kStreamStateBytes / 4u];
+    memcpy(r, row, sizeof r);
+    for (int i = 0; i < 8; i++) put_be32(out + 4 + 4 * i, r[i]);
+    const uint32_t fill = r[24] & 63u;
+    for (int i = 0; i < 16; i++) put_be32(out + 36 + 4 * i, r[8 + i]);
+    memset(out + 36 + fill, 0, 64u - fill);  // behind the fill the block's words are stale
+    put_be32(out + 100, r[25]);
+    put_be32(out + 104, r[24]);
+}
+void stream_unpack(const uint8_t* in, uint8_t* row) {
+    uint32_t r[kStreamStateBytes / 4u] = {};
+    for (int i = 0; i < 8; i++) r[i] = get_be32(in + 4 + 4 * i);
+    for (int i = 0; i < 16; i++) r[8 + i] = get_be32(in + 36 + 4 * i);
+    r[25] = get_be32(in + 100);
+    r[24] = get_be32(in + 104);
+    memcpy(row, r, sizeof r);
+}
+
+// The SHA-512/256 row.  A device row as u32 words: [h 8 x (lo, hi) | block 32 |
+// count lo, hi | 0, 0] (mirsha_sha512_streams.h); an exported state: the magic,
+// h as big-endian u64, the buffered bytes zero-padded to 128, the length as
+// big-endian u64.
+void sha512_stream_pack(const uint8_t* row, uint8_t* out) {
+    uint32_t r[kSha512StreamStateBytes / 4u];
+    memcpy(r, row, sizeof r);
+    for (int i = 0; i < 8; i++) {
+        put_be32(out + 4 + 8 * i, r[2 * i + 1]);
+        put_be32(out + 8 + 8 * i, r[2 * i]);
+    }
+    const uint32_t fill = r[48] & 127u;
+    for (int i = 0; i < 32; i++) put_be32(out + 68 + 4 * i, r[16 + i]);
+    memset(out + 68 + fill, 0, 128u - fill);
+    put_be32(out + 196, r[49]);
+    put_be32(out + 200, r[48]);
+}
+void sha512_stream_unpack(const uint8_t* in, uint8_t* row) {
+    uint32_t r[kSha512StreamStateBytes / 4u] = {};
+    for (int i = 0; i < 8; i++) {
+        r[2 * i + 1] = get_be32(in + 4 + 8 * i);
+        r[2 * i] = get_be32(in + 8 + 8 * i);
+    }
+    for (int i = 0; i < 32; i++) r[16 + i] = get_be32(in + 68 + 4 * i);
+    r[49] = get_be32(in + 196);
+    r[48] = get_be32(in + 200);
+    memcpy(row, r, sizeof r);
+}
+
+}  // namespace
+
+const StreamKernels& stream_kernels(int hasher) {
+    static const StreamKernels sha256 = {kStreamStateBytes, MIRSHA_STREAM_STATE_BYTES, {'s', 'h', 'a', 3},
+                                         stream_row0,       stream_pack,               stream_unpack,
+                                         launch_streams,    launch_streams_seg};
+    static const StreamKernels sha512_256 = {kSha512StreamStateBytes, MIRSHA_STREAM_STATE_BYTES_SHA512,
+                                             {'s', 'h', 'a', 6},      sha512_stream_row0,
+                                             sha512_stream_pack,      sha512_stream_unpack,
+                                             launch_sha512_streams,   launch_sha512_streams_seg};
+    return hasher == MIRSHA_HASHER_SHA512_256 ? sha512_256 : sha256;
+}
+
+}  // namespace mirsha
+
+namespace mirsha_api {
+
+namespace {
 
 // Both forms of mirsha_streams_run.  Order: every check and the plan (on the
 // host, before anything is queued), the block in one copy, one launch, the
@@ -86,9 +154,10 @@ int streams_run(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, bool on
     const uint8_t* dv = st->dev.as<uint8_t>();
     p.window(dv + o_bytes);
     if (int r = timed_launch(c, kTimerStreams, [&] {
-            return mirsha::launch_streams(p.words, p.shift, p.span, reinterpret_cast<const uint32_t*>(dv),
-                                          reinterpret_cast<const uint32_t*>(dv + o_ent), na, st->d_state.as<uint8_t>(),
-                                          st->d_out.as<uint8_t>(), c->stream);
+            return mirsha::stream_kernels(st->hasher).run(p.words, p.shift, p.span,
+                                                          reinterpret_cast<const uint32_t*>(dv),
+                                                          reinterpret_cast<const uint32_t*>(dv + o_ent), na,
+                                                          st->d_state.as<uint8_t>(), st->d_out.as<uint8_t>(), c->stream);
         }))
         return r;
     if (p.values)
@@ -112,21 +181,25 @@ int streams_which(mirsha_ctx* c, mirsha_streams* st, const uint32_t* which, uint
 
 extern "C" {
 
-int mirsha_streams_create(mirsha_ctx* c, uint32_t n, mirsha_streams** out) {
+int mirsha_streams_create_hasher(mirsha_ctx* c, uint32_t n, int hasher, mirsha_streams** out) {
     if (!c || !out) return MIRSHA_EINVAL;
     *out = nullptr;
+    if (hasher != MIRSHA_HASHER_SHA256 && hasher != MIRSHA_HASHER_SHA512_256)
+        return fail(c, MIRSHA_EINVAL, "unknown hasher %d", hasher);
     if (n == 0) return fail(c, MIRSHA_EINVAL, "n_streams must be > 0");
     if (int rc = use_device(c)) return rc;
     auto* st = new mirsha_streams();
     st->device = c->device;
     st->n = n;
-    constexpr uint32_t kWords = mirsha::kStreamStateBytes / 4u;
-    std::vector<uint32_t> rows((size_t)kWords * n, 0u);  // Hasher(): H0, nothing buffered, count 0
-    for (uint32_t i = 0; i < n; i++)
-        for (int j = 0; j < 8; j++) rows[(size_t)kWords * i + j] = mirsha::kH0[j];
+    st->hasher = hasher;
+    const mirsha::StreamKernels& kern = mirsha::stream_kernels(hasher);
+    st->row_bytes = kern.row_bytes;
+    std::vector<uint8_t> rows((size_t)kern.row_bytes * n);  // Hasher() for every stream: one row replicated
+    kern.row0(rows.data());
+    for (uint32_t i = 1; i < n; i++) memcpy(rows.data() + (size_t)kern.row_bytes * i, rows.data(), kern.row_bytes);
     auto up = [&]() -> int {
-        HIP_TRY(c, st->d_state.ensure(4ull * rows.size()));
-        HIP_TRY(c, hipMemcpyAsync(st->d_state.p, rows.data(), 4ull * rows.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, st->d_state.ensure(rows.size()));
+        HIP_TRY(c, hipMemcpyAsync(st->d_state.p, rows.data(), rows.size(), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         return MIRSHA_OK;
     };
@@ -135,6 +208,18 @@ int mirsha_streams_create(mirsha_ctx* c, uint32_t n, mirsha_streams** out) {
         return rc;
     }
     *out = st;
+    return MIRSHA_OK;
+}
+
+int mirsha_streams_create(mirsha_ctx* c, uint32_t n, mirsha_streams** out) {
+    return mirsha_streams_create_hasher(c, n, MIRSHA_HASHER_SHA256, out);
+}
+
+int mirsha_streams_hasher(const mirsha_streams* st) { return st ? st->hasher : MIRSHA_EINVAL; }
+
+int mirsha_stream_state_bytes(int hasher, uint32_t* bytes_out) {
+    if (hasher != MIRSHA_HASHER_SHA256 && hasher != MIRSHA_HASHER_SHA512_256) return MIRSHA_EINVAL;
+    if (bytes_out) *bytes_out = mirsha::stream_kernels(hasher).export_bytes;
     return MIRSHA_OK;
 }
 
@@ -150,7 +235,7 @@ void mirsha_streams_destroy(mirsha_streams* st) {
 int mirsha_streams_run(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, uint64_t arena_len,
                        const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                        const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = streams_hasher_match(c, st, __func__)) return rc;
     return streams_run(c, st, arena, false, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                        n_values_out);
 }
@@ -158,55 +243,48 @@ int mirsha_streams_run(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, 
 int mirsha_streams_run_device(mirsha_ctx* c, mirsha_streams* st, const uint8_t* d_arena, uint64_t arena_len,
                               const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                               const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = streams_hasher_match(c, st, __func__)) return rc;
     return streams_run(c, st, d_arena, true, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                        n_values_out);
 }
 
 int mirsha_streams_export(mirsha_ctx* c, mirsha_streams* st, const uint32_t* which, uint32_t k, uint8_t* out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = streams_hasher_match(c, st, __func__)) return rc;
     if (!c || !st) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (int rc = streams_which(c, st, which, k, out)) return rc;
     if (int rc = owner_order(c, st->ring)) return rc;
-    std::vector<uint32_t> rows((size_t)kRowWords * k);
+    const mirsha::StreamKernels& kern = mirsha::stream_kernels(st->hasher);
+    const size_t rb = kern.row_bytes;
+    std::vector<uint8_t> rows(rb * k);
     for (uint32_t j = 0; j < k; j++)
-        HIP_TRY(c, hipMemcpyAsync(&rows[(size_t)kRowWords * j], st->d_state.as<uint32_t>() + (uint64_t)kRowWords * which[j],
-                                  4u * kRowWords, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&rows[rb * j], st->d_state.as<uint8_t>() + rb * which[j], rb, hipMemcpyDeviceToHost,
+                                  c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (uint32_t j = 0; j < k; j++) {
-        const uint32_t* r = &rows[(size_t)kRowWords * j];  // [h 8 | block 16 | count lo, hi | 0, 0]
-        uint8_t* row = out + (uint64_t)kStateBytes * j;
-        memcpy(row, kStateMagic, 4);
-        for (int i = 0; i < 8; i++) put_be32(row + 4 + 4 * i, r[i]);
-        const uint32_t fill = r[24] & 63u;
-        for (int i = 0; i < 16; i++) put_be32(row + 36 + 4 * i, r[8 + i]);
-        memset(row + 36 + fill, 0, 64u - fill);  // behind the fill the block's words are stale
-        put_be32(row + 100, r[25]);
-        put_be32(row + 104, r[24]);
+        uint8_t* row = out + (uint64_t)kern.export_bytes * j;
+        memcpy(row, kern.magic, 4);
+        kern.pack(&rows[rb * j], row);
     }
     return MIRSHA_OK;
 }
 
 int mirsha_streams_import(mirsha_ctx* c, mirsha_streams* st, const uint32_t* which, uint32_t k, const uint8_t* in) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = streams_hasher_match(c, st, __func__)) return rc;
     if (!c || !st) return MIRSHA_EINVAL;
     if (k == 0) return MIRSHA_OK;
     if (int rc = streams_which(c, st, which, k, in)) return rc;
     if (int rc = owner_order(c, st->ring)) return rc;
+    const mirsha::StreamKernels& kern = mirsha::stream_kernels(st->hasher);
     for (uint32_t j = 0; j < k; j++)
-        if (memcmp(in + (uint64_t)kStateBytes * j, kStateMagic, 4) != 0)
-            return fail(c, MIRSHA_EINVAL, "state %u does not begin with \"sha\\x03\"", j);
-    std::vector<uint32_t> rows((size_t)kRowWords * k, 0u);
+        if (memcmp(in + (uint64_t)kern.export_bytes * j, kern.magic, 4) != 0)
+            return fail(c, MIRSHA_EINVAL, "state %u does not begin with \"sha\\x%02x\"", j, kern.magic[3]);
+    const size_t rb = kern.row_bytes;
+    std::vector<uint8_t> rows(rb * k);
     for (uint32_t j = 0; j < k; j++) {
-        const uint8_t* row = in + (uint64_t)kStateBytes * j;
-        uint32_t* r = &rows[(size_t)kRowWords * j];
-        for (int i = 0; i < 8; i++) r[i] = get_be32(row + 4 + 4 * i);
-        for (int i = 0; i < 16; i++) r[8 + i] = get_be32(row + 36 + 4 * i);
-        r[25] = get_be32(row + 100);
-        r[24] = get_be32(row + 104);
-        HIP_TRY(c, hipMemcpyAsync(st->d_state.as<uint32_t>() + (uint64_t)kRowWords * which[j], r, 4u * kRowWords,
-                                  hipMemcpyHostToDevice, c->stream));
+        kern.unpack(in + (uint64_t)kern.export_bytes * j, &rows[rb * j]);
+        HIP_TRY(c, hipMemcpyAsync(st->d_state.as<uint8_t>() + rb * which[j], &rows[rb * j], rb, hipMemcpyHostToDevice,
+                                  c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return MIRSHA_OK;

@@ -165,7 +165,7 @@ int streams_submit(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, bool
     t.n_seg = p.n_seg;
     t.stage_bytes = o_bytes + (on_device ? 0ull : p.bytes);
     t.dev_slack = kArenaSlack;  // the last word of the bytes lies inside
-    t.state[0] = {st->d_state.p, (uint64_t)mirsha::kStreamStateBytes * st->n};
+    t.state[0] = {st->d_state.p, (uint64_t)st->row_bytes * st->n};
     t.values_out = values_out;
     t.values = p.values;
     t.timer = kTimerStreams;
@@ -179,7 +179,7 @@ int streams_submit(mirsha_ctx* c, mirsha_streams* st, const uint8_t* arena, bool
         },
         [&](const uint8_t* dv, const uint8_t* const* state_in, uint8_t* rows, hipStream_t q) {
             p.window(dv + o_bytes);
-            return mirsha::launch_streams_seg(
+            return mirsha::stream_kernels(st->hasher).seg(
                 p.words, p.shift, p.span, reinterpret_cast<const uint32_t*>(dv),
                 reinterpret_cast<const uint32_t*>(dv + o_first), reinterpret_cast<const uint32_t*>(dv + o_flags),
                 reinterpret_cast<const uint32_t*>(dv + o_ent), p.n_seg, state_in[0], st->d_state.as<uint8_t>(), rows,
@@ -198,7 +198,7 @@ int mirsha_streams_submit(mirsha_ctx* c, mirsha_streams* st, const uint8_t* aren
                           const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                           const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
                           uint64_t* ticket_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = streams_hasher_match(c, st, __func__)) return rc;
     return streams_submit(c, st, arena, false, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                           n_values_out, ticket_out);
 }
@@ -207,7 +207,7 @@ int mirsha_streams_submit_device(mirsha_ctx* c, mirsha_streams* st, const uint8_
                                  const uint32_t* op_stream, const uint32_t* op_kind, const uint64_t* op_off,
                                  const uint32_t* op_len, uint32_t n_ops, uint8_t* values_out, uint32_t* n_values_out,
                                  uint64_t* ticket_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = streams_hasher_match(c, st, __func__)) return rc;
     return streams_submit(c, st, d_arena, true, arena_len, op_stream, op_kind, op_off, op_len, n_ops, values_out,
                           n_values_out, ticket_out);
 }

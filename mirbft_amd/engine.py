@@ -400,11 +400,11 @@ class Engine:
         """The hash function of the calls made from now on: "sha256" (default)
         or "sha512_256" (mirsha_ctx_set_hasher; the reference's `Hasher`,
         processor.go:21,58).  The hash, verify and ring calls honour it.
-        Checkpoint chains carry the hasher they were created with
-        (CheckpointChains, DeviceLog) and raise MirshaError (MIRSHA_EINVAL)
-        while the engine hashes with another one; plans and streams are
-        SHA-256 only and raise under any other hasher.  Tickets already
-        submitted keep the function they were queued with."""
+        Checkpoint chains and hash streams carry the hasher they were created
+        with (CheckpointChains, DeviceLog; HashStreams, StreamLog) and raise
+        MirshaError (MIRSHA_EINVAL) while the engine hashes with another one;
+        the device plans are SHA-256 only and raise under any other hasher.
+        Tickets already submitted keep the function they were queued with."""
         hasher = _hasher_id(hasher)
         self._check(self._lib.mirsha_ctx_set_hasher(self.ctx, hasher))
 
@@ -1089,8 +1089,30 @@ def stream_seg_plan(ops, n_streams: int, arena_len: int, pack: bool = False):
             ln[:ne.value], nv.value, nb.value, na.value)
 
 
+def stream_state_bytes(hasher: str | int) -> int:
+    """Bytes of one exported stream state under a hasher: 108 for "sha256",
+    204 for "sha512_256" (mirsha_stream_state_bytes; host only)."""
+    n = ctypes.c_uint32(0)
+    check(_lib.load().mirsha_stream_state_bytes(_hasher_id(hasher), ctypes.byref(n)))
+    return n.value
+
+
+class _StreamsHasher(str):
+    """``HashStreams.hasher``: the name of the streams' hash function, and,
+    called, a new hash.Hash-shaped object on a free stream (the method it was
+    before the streams had a hasher of their own)."""
+
+    def __new__(cls, name: str, streams: "HashStreams"):
+        self = super().__new__(cls, name)
+        self._streams = streams
+        return self
+
+    def __call__(self) -> "StreamHasher":
+        return self._streams._new_hasher()
+
+
 class HashStreams(_StateObject):
-    """Streaming SHA-256 states on the device (mirsha_streams_*): n hashers in
+    """Streaming hash states on the device (mirsha_streams_*): n hashers in
     the reference's own shape, ``type Hasher func() hash.Hash``
     (processor.go:21) -- Write any bytes any number of times, Sum at any point
     without disturbing the state, Reset -- whose midstate, unfinished block and
@@ -1100,16 +1122,26 @@ class HashStreams(_StateObject):
     the same as tickets of the engine's ring (one lane per stretch between
     resets, beside the hashing).  ``bytes_sent`` counts the bytes of the
     distinct ranges the write ops of each ``run`` / ``submit`` named (what
-    crossed PCIe); ``runs`` the calls."""
+    crossed PCIe); ``runs`` the calls.
+
+    The streams hash with ``hasher`` ("sha256" or "sha512_256"), fixed here;
+    ``None`` takes the engine's hasher as it is now.  Every call that runs,
+    submits, exports or imports raises MirshaError (MIRSHA_EINVAL) while the
+    engine hashes with another function.  ``.hasher`` is that name; called,
+    ``.hasher()``, it gives a hash.Hash-shaped object on a free stream."""
 
     _VALUES, _DESTROY = ("streams", "sums"), "mirsha_streams_destroy"
 
-    def __init__(self, engine: Engine, n_streams: int):
+    def __init__(self, engine: Engine, n_streams: int, hasher: str | int | None = None):
         self._engine = engine
         self._lib = engine._lib
+        hid = _hasher_id(engine.hasher if hasher is None else hasher)
         h = ctypes.c_void_p()
-        engine._check(self._lib.mirsha_streams_create(engine.ctx, int(n_streams), ctypes.byref(h)))
+        engine._check(self._lib.mirsha_streams_create_hasher(engine.ctx, int(n_streams), hid, ctypes.byref(h)))
         self.handle = h
+        self._hasher_name = {v: k for k, v in HASHERS.items()}[hid]
+        self.state_bytes = stream_state_bytes(hid)
+        self.digest_size, self.block_size = hasher_info(hid)
         self.n = int(n_streams)
         self.bytes_sent = 0
         self.runs = 0
@@ -1170,10 +1202,11 @@ class HashStreams(_StateObject):
                          keep, StreamTicket)
 
     def export_state(self, which) -> np.ndarray:
-        """The states of streams ``which`` as (k, 108) uint8 rows in the layout
-        of Go 1.14's crypto/sha256 MarshalBinary (mirsha_streams_export)."""
+        """The states of streams ``which`` as (k, ``state_bytes``) uint8 rows in
+        the layout of Go 1.14's MarshalBinary: crypto/sha256's (108 bytes) or,
+        for SHA-512/256 streams, crypto/sha512's (204) (mirsha_streams_export)."""
         w = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
-        out = np.empty((w.size, _lib.MIRSHA_STREAM_STATE_BYTES), dtype=np.uint8)
+        out = np.empty((w.size, self.state_bytes), dtype=np.uint8)
         if w.size:
             self._engine._check(self._lib.mirsha_streams_export(self._engine.ctx, self.handle, _ptr(w), w.size,
                                                                 _ptr(out)))
@@ -1185,18 +1218,23 @@ class HashStreams(_StateObject):
         w = np.ascontiguousarray(which, dtype=np.uint32).reshape(-1)
         if isinstance(states, (bytes, bytearray, memoryview)):
             states = np.frombuffer(bytes(states), dtype=np.uint8)
-        rows = np.ascontiguousarray(states, dtype=np.uint8).reshape(-1, _lib.MIRSHA_STREAM_STATE_BYTES)
+        rows = np.ascontiguousarray(states, dtype=np.uint8).reshape(-1, self.state_bytes)
         if rows.shape[0] != w.size:
-            raise ValueError("one 108-byte state per stream")
+            raise ValueError(f"one {self.state_bytes}-byte state per stream")
         if w.size:
             self._engine._check(self._lib.mirsha_streams_import(self._engine.ctx, self.handle, _ptr(w), w.size,
                                                                 _ptr(rows)))
 
     # ------------------------------------------------------- hash.Hash form
-    def hasher(self) -> "StreamHasher":
-        """A hash.Hash-shaped object bound to a free stream (``close()`` gives
-        the stream back).  Its first flush starts with a Reset, so it is
-        Hasher() whatever the stream held."""
+    @property
+    def hasher(self) -> "_StreamsHasher":
+        """The streams' hash function, "sha256" or "sha512_256"; called,
+        ``hasher()``, a hash.Hash-shaped object bound to a free stream
+        (``close()`` gives the stream back).  Its first flush starts with a
+        Reset, so it is Hasher() whatever the stream held."""
+        return _StreamsHasher(self._hasher_name, self)
+
+    def _new_hasher(self) -> "StreamHasher":
         if not self._free:
             raise MirshaError(_lib.MIRSHA_ERANGE, f"all {self.n} streams are in use")
         return StreamHasher(self, self._free.pop())
@@ -1245,13 +1283,12 @@ class StreamHasher:
     ``HashStreams``: ``write`` buffers on the host, ``sum`` sends only the
     bytes not sent yet plus a Sum (the state stays on the device, so a hasher
     summed after every write sends each byte once), ``reset`` is sent with the
-    next flush."""
-
-    size = 32
-    block_size = 64
+    next flush.  ``size`` / ``block_size`` are Go's Size() / BlockSize() of the
+    streams' hasher: 32 / 64 under SHA-256, 32 / 128 under SHA-512/256."""
 
     def __init__(self, streams: HashStreams, stream: int):
         self._streams = streams
+        self.size, self.block_size = streams.digest_size, streams.block_size
         self.stream = stream
         self._pending: list[bytes] = []
         self._reset = True

@@ -267,10 +267,16 @@ class StreamLog(_CycleLog):
     ``submit_cycle`` / ``collect_cycle`` are the asynchronous form
     (``HashStreams.submit``), with the contract of ``DeviceLog``'s: cycles take
     effect in submission order, whatever the order they are collected in.
-    ``DeviceLog`` stays the log for digest-only applications."""
+    ``DeviceLog`` stays the log for digest-only applications.
 
-    def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, entry_data=None, streams=None):
-        super().__init__(engine, n_nodes, node, streams, HashStreams)
+    As ``DeviceLog``'s chains, the streams hash with ``hasher`` ("sha256" or
+    "sha512_256"; None: the engine's hasher as it is when the log is made).
+    Make the log after the engine's hasher is set (``Processor(engine,
+    hasher=...)``): a log whose streams hash with another function than the
+    engine raises MirshaError (MIRSHA_EINVAL) at the first commit."""
+
+    def __init__(self, engine: Engine, n_nodes: int = 1, node: int = 0, entry_data=None, streams=None, hasher=None):
+        super().__init__(engine, n_nodes, node, streams, lambda eng, n: HashStreams(eng, n, hasher))
         self.entry_data = entry_data if entry_data is not None else batch_digests
         self.streams = self._state
         self._run, self._submit = self.streams.run, self.streams.submit
@@ -415,13 +421,12 @@ class Processor:
         """``hasher``: the reference's ``Hasher`` (processor.go:21,58) by name,
         "sha256" or "sha512_256"; it is set on the engine (``Engine.set_hasher``)
         and so holds for every user of that engine.  None leaves the engine's
-        hasher as it is (a new engine: "sha256").  A ``DeviceLog`` takes the
-        engine's hasher when it is made, so one made AFTER this Processor (and
-        set as its ``log``) hashes its checkpoints with the same function,
-        synchronously and with ``async_commits``; one made while the engine
-        still hashed with another function raises MirshaError (MIRSHA_EINVAL)
-        at the first commit.  Streams are SHA-256 only: a ``StreamLog`` on the
-        same engine raises at the first commit under any other hasher.
+        hasher as it is (a new engine: "sha256").  A ``DeviceLog`` or a
+        ``StreamLog`` takes the engine's hasher when it is made, so one made
+        AFTER this Processor (and set as its ``log``) hashes its checkpoints
+        with the same function, synchronously and with ``async_commits``; one
+        made while the engine still hashed with another function raises
+        MirshaError (MIRSHA_EINVAL) at the first commit.
         ``log``: the application log (p.Log, processor.go:147,163), e.g. a
         ``DeviceLog``: any object whose ``commit_cycle(commits)`` applies one
         cycle's commits and returns one value per checkpoint among them.
