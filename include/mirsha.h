@@ -457,6 +457,35 @@ int mirsha_pipeline_create(mirsha_ctx* ctx, uint32_t n_req, const uint32_t* len,
                            const uint32_t* list_first, uint32_t n_lists, mirsha_pipeline** out);
 int mirsha_pipeline_create_mode(mirsha_ctx* ctx, uint32_t n_req, const uint32_t* len, const uint32_t* idx,
                                 const uint32_t* list_first, uint32_t n_lists, int mode, mirsha_pipeline** out);
+/* A plan carries a hasher (MIRSHA_HASHER_*, "the context's hasher" below),
+ * fixed when it is created:
+ *   mirsha_pipeline_create / _create_mode: SHA-256 plans; refused with
+ *     MIRSHA_EINVAL under a context whose hasher is not SHA-256.
+ *   mirsha_pipeline_create_hasher: a plan of `hasher`, whatever the context's
+ *     hasher is now; MIRSHA_PIPELINE_MODE is not read.  An unknown hasher is
+ *     MIRSHA_EINVAL with a message that names it, *out = NULL.  With
+ *     MIRSHA_HASHER_SHA256 it is mirsha_pipeline_create_mode: the same
+ *     validation, builds, placement probe, launches and bytes.  With
+ *     MIRSHA_HASHER_SHA512_256: SEQUENTIAL is built sequential (the SHA-512/256
+ *     request kernel, then a list walk over the compacted lists, one lane per
+ *     list); AUTO is built SEQUENTIAL (mirsha_pipeline_mode reports it,
+ *     mirsha_pipeline_fallback 0); FUSED is MIRSHA_EINVAL with a message that
+ *     names the mode and the hasher, nothing allocated (no fused SHA-512/256
+ *     kernel is built).  _shape / _split_tiles / _trace / _status answer as for
+ *     any sequential plan.
+ *   mirsha_pipeline_hasher: the plan's hasher; MIRSHA_EINVAL for NULL.
+ * mirsha_hash_requests_then_batches_device and mirsha_pipeline_overlap_device
+ * are served when the context's hasher equals the plan's, else refused with
+ * MIRSHA_EINVAL ahead of any other effect, the message naming the call and both
+ * hashers.  A SHA-512/256 plan runs through one buffer descriptor: arena_len >
+ * 0xFFFFFF00 or n_req >= 2^27 is MIRSHA_ERANGE from both calls, checked on the
+ * host before anything is queued (there is no 64-bit-addressed SHA-512 form).
+ * Its overlapped cycle is one launch too: the workgroups of the previous
+ * cycle's lists first in the grid, then this cycle's request workgroups. */
+int mirsha_pipeline_create_hasher(mirsha_ctx* ctx, uint32_t n_req, const uint32_t* len, const uint32_t* idx,
+                                  const uint32_t* list_first, uint32_t n_lists, int mode, int hasher,
+                                  mirsha_pipeline** out);
+int mirsha_pipeline_hasher(const mirsha_pipeline* p);
 void mirsha_pipeline_destroy(mirsha_pipeline* p);
 int mirsha_pipeline_mode(const mirsha_pipeline* p);
 /* 1 if a FUSED (or AUTO -> fused) plan was built SEQUENTIAL instead because
@@ -625,14 +654,18 @@ int mirsha_ctx_order_mode(const mirsha_ctx* ctx);
  * equals the streams', and refused with MIRSHA_EINVAL and a message that names
  * the call and both hashers when it does not.  A stream ticket keeps the
  * function it was queued with.
+ * The device plans carry a hasher of their own in the same way
+ * (mirsha_pipeline_create_hasher): mirsha_hash_requests_then_batches_device and
+ * mirsha_pipeline_overlap_device are served when the context's hasher equals
+ * the plan's, and refused with MIRSHA_EINVAL and a message that names the call
+ * and both hashers when it does not.
  * Calls built for SHA-256 only refuse any other hasher at entry with
  * MIRSHA_EINVAL and a message that names the call and the hasher.  Either
  * refusal comes ahead of any other effect (state, ring and tickets stay as
  * they were; there is no silent SHA-256 and no CPU path).  SHA-256 only:
- * mirsha_pipeline_create / _create_mode,
- * mirsha_hash_requests_then_batches_device, mirsha_pipeline_overlap_device
- * (there is no SHA-512/256 form of the device plans).  The mirsha_multi_* forms
- * own their contexts, which stay SHA-256.
+ * mirsha_pipeline_create / _create_mode (they create SHA-256 plans; a
+ * SHA-512/256 plan comes from mirsha_pipeline_create_hasher, sequential form
+ * only).  The mirsha_multi_* forms own their contexts, which stay SHA-256.
  * mirsha_ctx_set_hasher: MIRSHA_EINVAL for a NULL context or an unknown value
  * (processor.go:21,58). */
 #define MIRSHA_HASHER_SHA256 0

@@ -145,6 +145,11 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_int, POINTER(c_void_p)],
     ),
+    "mirsha_pipeline_create_hasher": (
+        c_int,
+        [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_int, POINTER(c_void_p)],
+    ),
+    "mirsha_pipeline_hasher": (c_int, [c_void_p]),
     "mirsha_pipeline_destroy": (None, [c_void_p]),
     "mirsha_pipeline_mode": (c_int, [c_void_p]),
     "mirsha_pipeline_fallback": (c_int, [c_void_p]),

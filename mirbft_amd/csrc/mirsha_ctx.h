@@ -37,6 +37,9 @@
 //                       (mirsha_sha512_chains.h; chain_kernels, mirsha_chains.h)
 //   mirsha_sha512_streams.hip  its stream kernels
 //                       (mirsha_sha512_streams.h; stream_kernels, mirsha_streams.h)
+//   mirsha_sha512_plan.hip  its device-plan kernels: the plan-form list walk
+//                       and the overlapped cycle (mirsha_sha512_plan.h;
+//                       plan_kernels, mirsha_plan.hip)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
 // Digests[i] by the request's position), unlike ProcessorWorkPool's
@@ -63,6 +66,7 @@
 #include "mirsha_device.h"
 #include "mirsha_order.h"
 #include "mirsha_sha512.h"
+#include "mirsha_sha512_plan.h"
 
 namespace mirsha {
 // mirsha_expect.hip.  Mixed cycles (mirsha_submit_*_expect): compares the
@@ -336,6 +340,7 @@ struct mirsha_streams {
 struct mirsha_pipeline {
     int device = 0;
     int mode = MIRSHA_PIPELINE_FUSED;
+    int hasher = MIRSHA_HASHER_SHA256;  // fixed at creation (mirsha_pipeline_create_hasher): plan_kernels' case
     uint32_t n_req = 0, n_lists = 0, n_entries = 0;
     // fused mode (one persistent launch, see mirsha_kernels.hip)
     std::vector<uint32_t> tadj_first, tadj, cbase, expected;
@@ -432,7 +437,8 @@ inline hipError_t hasher_launch_lists(const mirsha_ctx* c, const uint8_t* digest
 
 inline const char* hasher_name(int hasher) { return hasher == MIRSHA_HASHER_SHA512_256 ? "sha512_256" : "sha256"; }
 
-// The entry guard of a call that is built for SHA-256 only (the device plans):
+// The entry guard of a call that is built for SHA-256 only (the two older
+// create calls of the device plans, mirsha_pipeline_create / _create_mode):
 // refused under any other hasher, ahead of any other effect.
 inline int sha256_only(mirsha_ctx* c, const char* call) {
     if (!c || c->hasher == MIRSHA_HASHER_SHA256) return MIRSHA_OK;  // (a NULL context is the call's own MIRSHA_EINVAL)
@@ -446,6 +452,15 @@ inline int sha256_only(mirsha_ctx* c, const char* call) {
 inline int chains_hasher_match(mirsha_ctx* c, const mirsha_chains* ch, const char* call) {
     if (!c || !ch || c->hasher == ch->hasher) return MIRSHA_OK;  // (NULL is the call's own MIRSHA_EINVAL)
     return fail(c, MIRSHA_EINVAL, "%s: the chains hash with %s, the context with %s", call, hasher_name(ch->hasher),
+                hasher_name(c->hasher));
+}
+
+// The same for the two run calls of a device plan
+// (mirsha_hash_requests_then_batches_device, mirsha_pipeline_overlap_device)
+// and the plan's own hasher.
+inline int plan_hasher_match(mirsha_ctx* c, const mirsha_pipeline* p, const char* call) {
+    if (!c || !p || c->hasher == p->hasher) return MIRSHA_OK;  // (NULL is the call's own MIRSHA_EINVAL)
+    return fail(c, MIRSHA_EINVAL, "%s: the plan hashes with %s, the context with %s", call, hasher_name(p->hasher),
                 hasher_name(c->hasher));
 }
 

@@ -1,6 +1,8 @@
 // mirsha_plan.hip — request -> batch-digest plans (mirsha_pipeline_*): the
 // sequential plan, the fused launch with its placement probe, and
-// overlapped cycles.
+// overlapped cycles.  A plan carries a hasher (mirsha_pipeline_create_hasher):
+// plan_kernels is the one place that maps it to kernels; under SHA-512/256 a
+// plan is sequential only.
 #include "mirsha_ctx.h"
 
 namespace mirsha_api {
@@ -75,26 +77,108 @@ int pipeline_build(mirsha_ctx* c, mirsha_pipeline* p, uint32_t n_req, const uint
     return MIRSHA_OK;
 }
 
+// The launches of a sequential plan and of a non-fused overlapped cycle, by the
+// plan's hasher: the one place that knows which kernels a plan's hasher means.
+// Each member launches at most one kernel (timed_launch).
+struct PlanKernels {
+    // this cycle's requests in the plan's order -> d_req_out
+    hipError_t (*requests)(const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len,
+                           const uint64_t* d_off, const uint32_t* d_len, uint8_t* d_req_out);
+    // the plan's compacted lists over d_digests (n_req rows) -> d_list_out; n_lists > 0
+    hipError_t (*lists)(const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_digests, uint8_t* d_list_out);
+    // one overlapped cycle: `tiles` = this cycle's requests -> d_req_out, `chains`
+    // = the lists over the previous cycle's d_prev_req -> d_prev_batch_out
+    hipError_t (*overlap)(const mirsha_ctx* c, const mirsha_pipeline* p, bool tiles, bool chains,
+                          const uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_off, const uint32_t* d_len,
+                          uint8_t* d_req_out, const uint8_t* d_prev_req, uint8_t* d_prev_batch_out);
+};
+
+const PlanKernels kPlanSha256 = {
+    [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_off,
+       const uint32_t* d_len, uint8_t* d_req_out) {
+        return mirsha::launch_msgs(d_arena, arena_len, d_off, d_len, p->d_order.as<uint32_t>(), p->n_req, d_req_out,
+                                   c->variant, c->stream);
+    },
+    [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_digests, uint8_t* d_list_out) {
+        if ((p->n_lists + 63u) / 64u <= mirsha::pair_max_groups())  // few long chains: producer/consumer pairs
+            return mirsha::launch_chain_pair(d_digests, p->n_req, p->d_cidx.as<uint32_t>(), p->n_entries,
+                                             p->d_cfirst.as<uint32_t>(), p->n_lists, d_list_out, c->stream);
+        return mirsha::launch_chain(d_digests, p->n_req, p->d_cidx.as<uint32_t>(), p->n_entries,
+                                    p->d_cfirst.as<uint32_t>(), p->n_lists, d_list_out, c->stream, p->uniform);
+    },
+    [](const mirsha_ctx* c, const mirsha_pipeline* p, bool tiles, bool chains, const uint8_t* d_arena,
+       uint64_t arena_len, const uint64_t* d_off, const uint32_t* d_len, uint8_t* d_req_out, const uint8_t* d_prev_req,
+       uint8_t* d_prev_batch_out) {
+        mirsha::OverlapArgs a{};
+        a.arena = d_arena;
+        a.arena_len = tiles ? arena_len : 0;
+        a.off = d_off;
+        a.len = d_len;
+        a.order = p->d_order.as<uint32_t>();
+        a.n_req = tiles ? p->n_req : 0u;
+        a.req_out = d_req_out;
+        a.prev_digests = d_prev_req;
+        a.n_req_prev = p->n_req;
+        a.cidx = p->d_cidx.as<uint32_t>();
+        a.n_entries = p->n_entries;
+        a.cfirst = p->d_cfirst.as<uint32_t>();
+        a.n_lists = p->n_lists;
+        a.list_out = d_prev_batch_out;
+        a.list_waves = chains ? (p->n_lists + 63u) / 64u : 0u;
+        if (const char* e = mirsha::ab_getenv("MIRSHA_OVERLAP_CHAIN_PRIO")) a.chain_prio = (uint32_t)atoi(e) & 3u;
+        return mirsha::launch_msgs_overlap(a, c->stream);
+    },
+};
+
+// SHA-512/256: one request kernel for every launch size, and every list shape
+// takes the plan-form walk (there is no producer/consumer pair route).
+const PlanKernels kPlanSha512 = {
+    [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_off,
+       const uint32_t* d_len, uint8_t* d_req_out) {
+        return mirsha::launch_sha512_msgs(d_arena, arena_len, d_off, d_len, p->d_order.as<uint32_t>(), p->n_req,
+                                          d_req_out, c->stream);
+    },
+    [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_digests, uint8_t* d_list_out) {
+        return mirsha::launch_sha512_plan_lists(d_digests, p->n_req, p->d_cidx.as<uint32_t>(), p->n_entries,
+                                                p->d_cfirst.as<uint32_t>(), p->n_lists, p->uniform, d_list_out,
+                                                c->stream);
+    },
+    [](const mirsha_ctx* c, const mirsha_pipeline* p, bool tiles, bool chains, const uint8_t* d_arena,
+       uint64_t arena_len, const uint64_t* d_off, const uint32_t* d_len, uint8_t* d_req_out, const uint8_t* d_prev_req,
+       uint8_t* d_prev_batch_out) {
+        mirsha::Sha512OverlapArgs a{};
+        a.arena = d_arena;
+        a.arena_len = tiles ? arena_len : 0;
+        a.off = d_off;
+        a.len = d_len;
+        a.order = p->d_order.as<uint32_t>();
+        a.n_req = tiles ? p->n_req : 0u;
+        a.req_out = d_req_out;
+        a.prev_digests = d_prev_req;
+        a.n_req_prev = p->n_req;
+        a.cidx = p->d_cidx.as<uint32_t>();
+        a.n_entries = p->n_entries;
+        a.cfirst = p->d_cfirst.as<uint32_t>();
+        a.n_lists = chains ? p->n_lists : 0u;
+        a.uniform = p->uniform;
+        a.list_out = d_prev_batch_out;
+        return mirsha::launch_sha512_overlap(a, c->stream);
+    },
+};
+
+const PlanKernels& plan_kernels(const mirsha_pipeline* p) {
+    return p->hasher == MIRSHA_HASHER_SHA512_256 ? kPlanSha512 : kPlanSha256;
+}
+
 int pipeline_run(mirsha_ctx* c, mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_off,
                  const uint32_t* d_len, uint8_t* d_req_out, uint8_t* d_list_out) {
-    const uint32_t* order = p->d_order.as<uint32_t>();
+    const PlanKernels& k = plan_kernels(p);
     if (p->n_req) {
-        if (int rc = timed_launch(c, 0, [&] {
-                return mirsha::launch_msgs(d_arena, arena_len, d_off, d_len, order, p->n_req, d_req_out, c->variant,
-                                           c->stream);
-            }))
+        if (int rc = timed_launch(c, 0, [&] { return k.requests(c, p, d_arena, arena_len, d_off, d_len, d_req_out); }))
             return rc;
     }
     if (p->n_lists == 0) return MIRSHA_OK;
-    if ((p->n_lists + 63u) / 64u <= mirsha::pair_max_groups())
-        return timed_launch(c, 1, [&] {  // few long chains: producer/consumer pairs
-            return mirsha::launch_chain_pair(d_req_out, p->n_req, p->d_cidx.as<uint32_t>(), p->n_entries,
-                                             p->d_cfirst.as<uint32_t>(), p->n_lists, d_list_out, c->stream);
-        });
-    return timed_launch(c, 1, [&] {
-        return mirsha::launch_chain(d_req_out, p->n_req, p->d_cidx.as<uint32_t>(), p->n_entries,
-                                    p->d_cfirst.as<uint32_t>(), p->n_lists, d_list_out, c->stream, p->uniform);
-    });
+    return timed_launch(c, 1, [&] { return k.lists(c, p, d_req_out, d_list_out); });
 }
 
 
@@ -492,6 +576,35 @@ void pipeline_free(mirsha_pipeline* p) {
     p->h_err = p->d_err = nullptr;
 }
 
+// The one creation path: checks, then the build of `mode` under `hasher`.
+// SHA-512/256 has the sequential build only (AUTO means it; FUSED is refused by
+// the caller before this).
+int pipeline_create(mirsha_ctx* c, uint32_t n_req, const uint32_t* len, const uint32_t* idx, const uint32_t* list_first,
+                    uint32_t n_lists, int mode, int hasher, mirsha_pipeline** out) {
+    if (mode != MIRSHA_PIPELINE_SEQUENTIAL && mode != MIRSHA_PIPELINE_FUSED && mode != MIRSHA_PIPELINE_AUTO)
+        return fail(c, MIRSHA_EINVAL, "bad pipeline mode %d (sequential 0, fused 1, auto 3)", mode);
+    if (int rc = check_lists(c, idx, list_first, n_lists, n_req)) return rc;
+    if (int rc = use_device(c)) return rc;
+    mirsha_pipeline* p = new mirsha_pipeline();
+    p->device = c->device;
+    p->mode = mode;
+    p->hasher = hasher;
+    int rc;
+    if (hasher == MIRSHA_HASHER_SHA256) {
+        rc = plan_build(c, p, n_req, idx, list_first, n_lists, len);
+    } else {
+        p->mode = MIRSHA_PIPELINE_SEQUENTIAL;
+        rc = pipeline_build(c, p, n_req, idx, list_first, n_lists, len);
+    }
+    if (rc != MIRSHA_OK) {
+        pipeline_free(p);
+        delete p;
+        return rc;
+    }
+    *out = p;
+    return MIRSHA_OK;
+}
+
 }  // namespace mirsha_api
 
 extern "C" {
@@ -507,22 +620,23 @@ int mirsha_pipeline_create_mode(mirsha_ctx* c, uint32_t n_req, const uint32_t* l
     if (int rc = sha256_only(c, __func__)) return rc;
     if (!c || !out) return MIRSHA_EINVAL;
     *out = nullptr;
-    if (mode != MIRSHA_PIPELINE_SEQUENTIAL && mode != MIRSHA_PIPELINE_FUSED && mode != MIRSHA_PIPELINE_AUTO)
-        return fail(c, MIRSHA_EINVAL, "bad pipeline mode %d (sequential 0, fused 1, auto 3)", mode);
-    if (int rc = check_lists(c, idx, list_first, n_lists, n_req)) return rc;
-    if (int rc = use_device(c)) return rc;
-    mirsha_pipeline* p = new mirsha_pipeline();
-    p->device = c->device;
-    p->mode = mode;
-    int rc = plan_build(c, p, n_req, idx, list_first, n_lists, len);
-    if (rc != MIRSHA_OK) {
-        pipeline_free(p);
-        delete p;
-        return rc;
-    }
-    *out = p;
-    return MIRSHA_OK;
+    return pipeline_create(c, n_req, len, idx, list_first, n_lists, mode, MIRSHA_HASHER_SHA256, out);
 }
+
+int mirsha_pipeline_create_hasher(mirsha_ctx* c, uint32_t n_req, const uint32_t* len, const uint32_t* idx,
+                                  const uint32_t* list_first, uint32_t n_lists, int mode, int hasher,
+                                  mirsha_pipeline** out) {
+    if (!c || !out) return MIRSHA_EINVAL;
+    *out = nullptr;
+    if (hasher != MIRSHA_HASHER_SHA256 && hasher != MIRSHA_HASHER_SHA512_256)
+        return fail(c, MIRSHA_EINVAL, "unknown hasher %d (sha256 0, sha512_256 1)", hasher);
+    if (hasher != MIRSHA_HASHER_SHA256 && mode == MIRSHA_PIPELINE_FUSED)
+        return fail(c, MIRSHA_EINVAL, "pipeline mode fused is not built for hasher %s (sequential 0 or auto 3)",
+                    hasher_name(hasher));
+    return pipeline_create(c, n_req, len, idx, list_first, n_lists, mode, hasher, out);
+}
+
+int mirsha_pipeline_hasher(const mirsha_pipeline* p) { return p ? p->hasher : MIRSHA_EINVAL; }
 
 void mirsha_pipeline_destroy(mirsha_pipeline* p) {
     if (!p) return;
@@ -581,12 +695,19 @@ int mirsha_pipeline_status(mirsha_ctx* c, mirsha_pipeline* p) {
 int mirsha_hash_requests_then_batches_device(mirsha_ctx* c, mirsha_pipeline* p, const uint8_t* d_arena,
                                              uint64_t arena_len, const uint64_t* d_off, const uint32_t* d_len,
                                              uint8_t* d_req_out, uint8_t* d_batch_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = plan_hasher_match(c, p, __func__)) return rc;
     if (!c || !p) return MIRSHA_EINVAL;
     if (p->device != c->device) return fail(c, MIRSHA_EINVAL, "pipeline built for device %d", p->device);
     if (p->n_req && (!d_off || !d_len || !d_req_out || (!d_arena && arena_len))) return fail(c, MIRSHA_EINVAL, "NULL argument");
     if (p->n_lists && !d_batch_out) return fail(c, MIRSHA_EINVAL, "NULL batch output");
     if (arena_len > MIRSHA_MAX_DEVICE_ARENA_BYTES) return fail(c, MIRSHA_ERANGE, "device arena too large");
+    if (p->hasher == MIRSHA_HASHER_SHA512_256) {  // one descriptor: mirsha_hash_batch_device's limits under this hasher
+        if (arena_len > mirsha::kMaxBufferArena)
+            return fail(c, MIRSHA_ERANGE, "%s: arena > %llu bytes under hasher sha512_256", __func__,
+                        (unsigned long long)mirsha::kMaxBufferArena);
+        if (p->n_req >= mirsha::kMaxBufferMsgs)
+            return fail(c, MIRSHA_ERANGE, "%s: %u requests under hasher sha512_256", __func__, p->n_req);
+    }
     if (int rc = use_device(c)) return rc;
     return plan_run(c, p, d_arena, arena_len, d_off, d_len, d_req_out, d_batch_out);
 }
@@ -594,7 +715,7 @@ int mirsha_hash_requests_then_batches_device(mirsha_ctx* c, mirsha_pipeline* p, 
 int mirsha_pipeline_overlap_device(mirsha_ctx* c, mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len,
                                    const uint64_t* d_off, const uint32_t* d_len, uint8_t* d_req_out,
                                    const uint8_t* d_prev_req, uint8_t* d_prev_batch_out) {
-    if (int rc = sha256_only(c, __func__)) return rc;
+    if (int rc = plan_hasher_match(c, p, __func__)) return rc;
     if (!c || !p) return MIRSHA_EINVAL;
     if (p->device != c->device) return fail(c, MIRSHA_EINVAL, "pipeline built for device %d", p->device);
     const bool tiles = d_req_out != nullptr && p->n_req;
@@ -620,24 +741,10 @@ int mirsha_pipeline_overlap_device(mirsha_ctx* c, mirsha_pipeline* p, const uint
                                                          (unsigned long long)mirsha::kMaxBufferArena);
     if (p->n_req >= mirsha::kMaxBufferMsgs) return fail(c, MIRSHA_ERANGE, "overlap: %u requests", p->n_req);
     if (int rc = use_device(c)) return rc;
-    mirsha::OverlapArgs a{};
-    a.arena = d_arena;
-    a.arena_len = tiles ? arena_len : 0;
-    a.off = d_off;
-    a.len = d_len;
-    a.order = p->d_order.as<uint32_t>();
-    a.n_req = tiles ? p->n_req : 0u;
-    a.req_out = d_req_out;
-    a.prev_digests = d_prev_req;
-    a.n_req_prev = p->n_req;
-    a.cidx = p->d_cidx.as<uint32_t>();
-    a.n_entries = p->n_entries;
-    a.cfirst = p->d_cfirst.as<uint32_t>();
-    a.n_lists = p->n_lists;
-    a.list_out = d_prev_batch_out;
-    a.list_waves = chains ? (p->n_lists + 63u) / 64u : 0u;
-    if (const char* e = mirsha::ab_getenv("MIRSHA_OVERLAP_CHAIN_PRIO")) a.chain_prio = (uint32_t)atoi(e) & 3u;
-    return timed_launch(c, 5, [&] { return mirsha::launch_msgs_overlap(a, c->stream); });
+    return timed_launch(c, 5, [&] {
+        return plan_kernels(p).overlap(c, p, tiles, chains, d_arena, arena_len, d_off, d_len, d_req_out, d_prev_req,
+                                       d_prev_batch_out);
+    });
 }
 
 }  // extern "C"

@@ -835,7 +835,7 @@ int mirsha_hash_requests_then_batches(mirsha_ctx* c, const uint8_t* arena, uint6
     // uses a plan only when asked (MIRSHA_PIPELINE_MODE=fused|auto); the
     // device API (mirsha_pipeline_create + *_device) amortises one plan.
     const char* pmode = getenv("MIRSHA_PIPELINE_MODE");
-    // (the plans are SHA-256 only: any other hasher takes the staged route)
+    // (this host call builds SHA-256 plans only: any other hasher takes the staged route)
     const bool pipelined = c->hasher == MIRSHA_HASHER_SHA256 && pmode &&
                            (strcmp(pmode, "fused") == 0 || strcmp(pmode, "auto") == 0);
     uint64_t lo = 0, hi = 0, total = 0;

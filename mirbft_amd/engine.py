@@ -403,7 +403,9 @@ class Engine:
         Checkpoint chains and hash streams carry the hasher they were created
         with (CheckpointChains, DeviceLog; HashStreams, StreamLog) and raise
         MirshaError (MIRSHA_EINVAL) while the engine hashes with another one;
-        the device plans are SHA-256 only and raise under any other hasher.
+        so do the device plans (``pipeline(..., hasher=...)``; without
+        ``hasher`` a plan is SHA-256 and its creation raises under any other
+        hasher).
         Tickets already submitted keep the function they were queued with."""
         hasher = _hasher_id(hasher)
         self._check(self._lib.mirsha_ctx_set_hasher(self.ctx, hasher))
@@ -754,10 +756,16 @@ class Engine:
         self._check(self._lib.mirsha_digest_lists_device(self.ctx, d_digests, n_digests, d_idx, d_first, n_lists,
                                                          n_entries, d_out))
 
-    def pipeline(self, n_req: int, idx, list_first, length=None, mode: int | str | None = None) -> "Pipeline":
+    def pipeline(self, n_req: int, idx, list_first, length=None, mode: int | str | None = None,
+                 hasher: str | int | None = None) -> "Pipeline":
         """Plan for request -> batch-digest runs with this list shape (host index lists).
-        mode: PIPELINE_AUTO (default) / _FUSED / _SEQUENTIAL or its name."""
-        return Pipeline(self, n_req, idx, list_first, length, mode)
+        mode: PIPELINE_AUTO (default) / _FUSED / _SEQUENTIAL or its name.
+        hasher: "sha256" / "sha512_256" or its id: the plan hashes with it,
+        whatever the engine's hasher is now (mirsha_pipeline_create_hasher;
+        mode None = AUTO; under "sha512_256" a plan is sequential, "fused"
+        raises), and runs only while the engine hashes with the same one.
+        None: a SHA-256 plan by mirsha_pipeline_create / _create_mode."""
+        return Pipeline(self, n_req, idx, list_first, length, mode, hasher)
 
     def hash_requests_then_batches_device(self, plan: "Pipeline", d_arena: int, arena_len: int, d_off: int,
                                           d_len: int, d_req_out: int, d_batch_out: int) -> None:
@@ -805,14 +813,20 @@ class Pipeline:
     """mirsha_pipeline: a request -> batch-digest plan reused across runs of one
     shape (see include/mirsha.h for the modes)."""
 
-    def __init__(self, engine: Engine, n_req: int, idx, list_first, length=None, mode=None):
+    def __init__(self, engine: Engine, n_req: int, idx, list_first, length=None, mode=None, hasher=None):
         self._lib = engine._lib
         self._engine = engine
         ix = np.ascontiguousarray(idx, dtype=np.uint32)
         fs = np.ascontiguousarray(list_first, dtype=np.uint32)
         ln = None if length is None else np.ascontiguousarray(length, dtype=np.uint32)
         h = ctypes.c_void_p()
-        if mode is None:
+        if hasher is not None:
+            # (an unknown id goes to the library, whose refusal names it)
+            hid = _hasher_id(hasher) if isinstance(hasher, str) else int(hasher)
+            m = PIPELINE_AUTO if mode is None else PIPELINE_MODES[mode] if isinstance(mode, str) else int(mode)
+            engine._check(self._lib.mirsha_pipeline_create_hasher(engine.ctx, int(n_req), _ptr(ln), _ptr(ix),
+                                                                  _ptr(fs), int(fs.size) - 1, m, hid, ctypes.byref(h)))
+        elif mode is None:
             engine._check(self._lib.mirsha_pipeline_create(engine.ctx, int(n_req), _ptr(ln), _ptr(ix), _ptr(fs),
                                                            int(fs.size) - 1, ctypes.byref(h)))
         else:
@@ -830,6 +844,14 @@ class Pipeline:
     @property
     def mode_name(self) -> str:
         return {v: k for k, v in PIPELINE_MODES.items()}[self.mode]
+
+    @property
+    def hasher(self) -> str:
+        """The name of the plan's hash function (mirsha_pipeline_hasher)."""
+        h = self._lib.mirsha_pipeline_hasher(self.handle)
+        if h < 0:
+            check(h)
+        return {v: k for k, v in HASHERS.items()}[h]
 
     def status(self) -> None:
         """Synchronise and raise if a fused run's readiness watchdog expired."""
