@@ -88,7 +88,11 @@ void* mirsha_ctx_stream(mirsha_ctx* ctx);
  *     later workgroups, one CU at a time).
  * All of these are bit-exact.  Anything else is EINVAL: 2, 3, 7, 8 (round-1
  * A/B forms) and 11-15 (earlier and diagnostic forms of the CU-block kernel)
- * are retired: no build holds them, whatever the environment says. */
+ * are retired: no build holds them, whatever the environment says.
+ * Under MIRSHA_HASHER_SHA512_256 the request launch reads the same value:
+ * 6 = the SHA-512/256 pair kernel at any size, 1 and 5 = the one-lane kernel
+ * at any size, every other accepted value = automatic (the pair kernel for at
+ * most mirsha_sha512_pair_max_groups() groups, else the one-lane kernel). */
 int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
 
 /* Per-kernel device-time accounting with HIP events bound to each timed
@@ -677,6 +681,18 @@ int mirsha_ctx_hasher(const mirsha_ctx* ctx);
  * MIRSHA_HASHER_SHA256, 32 / 128 for MIRSHA_HASHER_SHA512_256.  Host only, no
  * context; either pointer may be NULL.  MIRSHA_EINVAL: an unknown hasher. */
 int mirsha_hasher_info(int hasher, uint32_t* digest_bytes, uint32_t* block_bytes);
+/* The producer/consumer pair route of MIRSHA_HASHER_SHA512_256: a request,
+ * list or sequential-plan list launch of at most this many 64-lane groups
+ * (256 by default, one pair per CU: the largest measured count at which the
+ * pair beat the one-lane kernels) splits every compression over
+ * two waves, schedule and rounds; a larger launch takes the one-lane kernels.  Bit-exact either way.  Host only,
+ * no context, like mirsha_hasher_info: the threshold in force (the A/B knobs
+ * MIRSHA_SHA512_PAIR=0 and MIRSHA_SHA512_PAIR_MAX_GROUPS=n move it, read only
+ * with MIRSHA_AB=1). */
+int mirsha_sha512_pair_max_groups(void);
+/* Pair launches (request, list and plan-list kernels) queued by this context
+ * since its creation.  MIRSHA_EINVAL for a NULL context or a NULL out. */
+int mirsha_ctx_sha512_pair_launches(const mirsha_ctx* ctx, uint64_t* out);
 
 /* ------------------------------------- streaming checkpoint chains (f4) */
 /* Device-resident running hash states, one per application node: the

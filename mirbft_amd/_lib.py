@@ -140,6 +140,8 @@ SIGNATURES = {
     "mirsha_ctx_set_hasher": (c_int, [c_void_p, c_int]),
     "mirsha_ctx_hasher": (c_int, [c_void_p]),
     "mirsha_hasher_info": (c_int, [c_int, _u32p, _u32p]),
+    "mirsha_sha512_pair_max_groups": (c_int, []),
+    "mirsha_ctx_sha512_pair_launches": (c_int, [c_void_p, _u64p]),
     "mirsha_pipeline_create": (c_int, [c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
     "mirsha_pipeline_create_mode": (
         c_int,

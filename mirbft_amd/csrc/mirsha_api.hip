@@ -392,6 +392,14 @@ int mirsha_hasher_info(int hasher, uint32_t* digest_bytes, uint32_t* block_bytes
     return MIRSHA_OK;
 }
 
+int mirsha_sha512_pair_max_groups(void) { return (int)mirsha::sha512_pair_max_groups(); }
+
+int mirsha_ctx_sha512_pair_launches(const mirsha_ctx* c, uint64_t* out) {
+    if (!c || !out) return MIRSHA_EINVAL;
+    *out = c->sha512_pair_launches;
+    return MIRSHA_OK;
+}
+
 int mirsha_synth_mixed_lengths_device(mirsha_ctx* c, uint64_t seed, uint64_t first, uint64_t count,
                                       uint32_t* d_len) {
     if (!c) return MIRSHA_EINVAL;

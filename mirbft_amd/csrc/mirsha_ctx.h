@@ -40,6 +40,10 @@
 //   mirsha_sha512_plan.hip  its device-plan kernels: the plan-form list walk
 //                       and the overlapped cycle (mirsha_sha512_plan.h;
 //                       plan_kernels, mirsha_plan.hip)
+//   mirsha_sha512_pair.hip  its producer/consumer pair kernels for small
+//                       launches and the routed launchers that choose between
+//                       them and the one-lane kernels (mirsha_sha512_pair.h;
+//                       hasher_launch_* below, plan_kernels)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
 // Digests[i] by the request's position), unlike ProcessorWorkPool's
@@ -66,6 +70,7 @@
 #include "mirsha_device.h"
 #include "mirsha_order.h"
 #include "mirsha_sha512.h"
+#include "mirsha_sha512_pair.h"
 #include "mirsha_sha512_plan.h"
 
 namespace mirsha {
@@ -251,6 +256,10 @@ struct mirsha_ctx {
     hipStream_t stream = nullptr;
     int variant = mirsha::kVariantLds;
     int hasher = MIRSHA_HASHER_SHA256;  // mirsha_ctx_set_hasher: which kernels hasher_launch_* queue
+    // SHA-512/256 launches that took the producer/consumer pair kernels
+    // (mirsha_ctx_sha512_pair_launches); counted where a launch is queued, which
+    // holds the context const.
+    mutable uint64_t sha512_pair_launches = 0;
     bool timing = false;
     uint32_t time_mask = 0xFFFFFFFFu;  // kernels timed while timing is on
     std::string err;
@@ -419,19 +428,23 @@ int timed_launch(mirsha_ctx* c, int which, F&& launch) {
 // The context's hasher (mirsha_ctx_set_hasher) decides which kernel a hashing
 // launch queues; the callers pass what launch_msgs / launch_lists take and
 // know nothing else about hashers.  Timing ids 0 and 1 are by role (request
-// kernel, list kernel), so the callers keep them.
+// kernel, list kernel), so the callers keep them.  Under SHA-512/256 the
+// routed launchers (mirsha_sha512_pair.h) pick the pair or the one-lane kernel
+// by the launch's size and the context's variant, one kernel either way.
 inline hipError_t hasher_launch_msgs(const mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len,
                                      const uint64_t* off, const uint32_t* len, const uint32_t* order, uint32_t n,
                                      uint8_t* out, hipStream_t s) {
     if (c->hasher == MIRSHA_HASHER_SHA512_256)
-        return mirsha::launch_sha512_msgs(arena, arena_len, off, len, order, n, out, s);
+        return mirsha::launch_sha512_msgs(arena, arena_len, off, len, order, n, out, c->variant, s,
+                                          &c->sha512_pair_launches);
     return mirsha::launch_msgs(arena, arena_len, off, len, order, n, out, c->variant, s);
 }
 inline hipError_t hasher_launch_lists(const mirsha_ctx* c, const uint8_t* digests, uint32_t n_digests,
                                       const uint32_t* idx, uint32_t n_entries, const uint32_t* first, uint32_t n_lists,
                                       uint32_t* scratch, uint8_t* out, hipStream_t s) {
     if (c->hasher == MIRSHA_HASHER_SHA512_256)
-        return mirsha::launch_sha512_lists(digests, n_digests, idx, n_entries, first, n_lists, scratch, out, s);
+        return mirsha::launch_sha512_lists(digests, n_digests, idx, n_entries, first, n_lists, scratch, out, s,
+                                           &c->sha512_pair_launches);
     return mirsha::launch_lists(digests, n_digests, idx, n_entries, first, n_lists, scratch, out, s);
 }
 

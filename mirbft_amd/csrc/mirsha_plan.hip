@@ -130,18 +130,21 @@ const PlanKernels kPlanSha256 = {
     },
 };
 
-// SHA-512/256: one request kernel for every launch size, and every list shape
-// takes the plan-form walk (there is no producer/consumer pair route).
+// SHA-512/256: the routed launchers of mirsha_sha512_pair.h.  Requests follow
+// the context's variant as launch_msgs does; few long lists ((n_lists + 63) /
+// 64 <= sha512_pair_max_groups(), the rule of kPlanSha256.lists) take the
+// producer/consumer pairs, any other the one-lane plan-form walk.  The
+// overlapped cycle has no pair form.
 const PlanKernels kPlanSha512 = {
     [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_off,
        const uint32_t* d_len, uint8_t* d_req_out) {
         return mirsha::launch_sha512_msgs(d_arena, arena_len, d_off, d_len, p->d_order.as<uint32_t>(), p->n_req,
-                                          d_req_out, c->stream);
+                                          d_req_out, c->variant, c->stream, &c->sha512_pair_launches);
     },
     [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_digests, uint8_t* d_list_out) {
         return mirsha::launch_sha512_plan_lists(d_digests, p->n_req, p->d_cidx.as<uint32_t>(), p->n_entries,
                                                 p->d_cfirst.as<uint32_t>(), p->n_lists, p->uniform, d_list_out,
-                                                c->stream);
+                                                c->stream, &c->sha512_pair_launches);
     },
     [](const mirsha_ctx* c, const mirsha_pipeline* p, bool tiles, bool chains, const uint8_t* d_arena,
        uint64_t arena_len, const uint64_t* d_off, const uint32_t* d_len, uint8_t* d_req_out, const uint8_t* d_prev_req,

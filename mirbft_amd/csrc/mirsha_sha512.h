@@ -1,7 +1,8 @@
 // mirsha_sha512.h — launchers of the SHA-512/256 kernels (mirsha_sha512.hip):
 // the request and the list kernel of a context whose hasher is
-// MIRSHA_HASHER_SHA512_256 (hasher_launch_msgs / _lists, mirsha_ctx.h).  Not
-// part of the C-ABI.
+// MIRSHA_HASHER_SHA512_256: the one-lane kernels, which the routed launchers of
+// mirsha_sha512_pair.h (what hasher_launch_msgs / _lists queue, mirsha_ctx.h)
+// take for every launch that is not small.  Not part of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -76,6 +76,13 @@ def hasher_info(hasher: str | int) -> tuple[int, int]:
     return size.value, block.value
 
 
+def sha512_pair_max_groups() -> int:
+    """The largest launch, in 64-lane groups, that takes the producer/consumer
+    pair kernels under "sha512_256" (mirsha_sha512_pair_max_groups; host only,
+    no device needed).  0: the automatic route is off."""
+    return int(_lib.load().mirsha_sha512_pair_max_groups())
+
+
 def _as_u8(buf) -> np.ndarray:
     if isinstance(buf, np.ndarray):
         return np.ascontiguousarray(buf.reshape(-1).view(np.uint8))
@@ -416,6 +423,15 @@ class Engine:
         if h < 0:
             self._check(h)
         return {v: k for k, v in HASHERS.items()}[h]
+
+    @property
+    def sha512_pair_launches(self) -> int:
+        """Launches of this engine that took the SHA-512/256 producer/consumer
+        pair kernels (requests, lists and plan lists) since its creation
+        (mirsha_ctx_sha512_pair_launches)."""
+        n = ctypes.c_uint64(0)
+        self._check(self._lib.mirsha_ctx_sha512_pair_launches(self.ctx, ctypes.byref(n)))
+        return n.value
 
     def set_timing(self, enable: bool) -> None:
         self._check(self._lib.mirsha_ctx_set_timing(self.ctx, 1 if enable else 0))
