@@ -92,7 +92,11 @@ void* mirsha_ctx_stream(mirsha_ctx* ctx);
  * Under MIRSHA_HASHER_SHA512_256 the request launch reads the same value:
  * 6 = the SHA-512/256 pair kernel at any size, 1 and 5 = the one-lane kernel
  * at any size, every other accepted value = automatic (the pair kernel for at
- * most mirsha_sha512_pair_max_groups() groups, else the one-lane kernel). */
+ * most mirsha_sha512_pair_max_groups() groups, else the one-lane kernel).
+ * The commit launches of SHA-512/256 checkpoint chains (mirsha_chains_absorb,
+ * mirsha_chains_commit*, mirsha_chains_commit_submit*) read it in the same
+ * way, when the call or the ticket is queued: one lane per active chain or per
+ * segment, 64 of them a group. */
 int mirsha_ctx_set_variant(mirsha_ctx* ctx, int variant);
 
 /* Per-kernel device-time accounting with HIP events bound to each timed
@@ -691,7 +695,11 @@ int mirsha_hasher_info(int hasher, uint32_t* digest_bytes, uint32_t* block_bytes
  * with MIRSHA_AB=1). */
 int mirsha_sha512_pair_max_groups(void);
 /* Pair launches (request, list and plan-list kernels) queued by this context
- * since its creation.  MIRSHA_EINVAL for a NULL context or a NULL out. */
+ * since its creation.  MIRSHA_EINVAL for a NULL context or a NULL out.  The
+ * commit launches of checkpoint chains take the same route by the same
+ * threshold (the walk of a chain's entries on the producer's side, h and the
+ * rounds on the consumer's) but are counted per chains object, not here:
+ * mirsha_chains_pair_launches. */
 int mirsha_ctx_sha512_pair_launches(const mirsha_ctx* ctx, uint64_t* out);
 
 /* ------------------------------------- streaming checkpoint chains (f4) */
@@ -707,6 +715,11 @@ int mirsha_ctx_sha512_pair_launches(const mirsha_ctx* ctx, uint64_t* out);
  *     words, up to three pending digests (four fill a 128-byte block) and the
  *     digest count.
  *   mirsha_chains_hasher: the chains' hasher; MIRSHA_EINVAL for NULL.
+ *   mirsha_chains_pair_launches: commit launches of these chains (absorb, the
+ *     commit calls and the commit tickets below) that took the SHA-512/256
+ *     producer/consumer pair kernels, counted since creation where the launch
+ *     is queued.  Always 0 for SHA-256 chains.  MIRSHA_EINVAL for a NULL
+ *     argument; *out is left as it was.
  * Every hashing call on the chains (absorb, sum, the commit calls below) needs
  * a context whose hasher is the chains' own, else MIRSHA_EINVAL ahead of any
  * other effect; mirsha_chains_reset hashes nothing and is served under either.
@@ -721,6 +734,7 @@ typedef struct mirsha_chains mirsha_chains;
 int mirsha_chains_create(mirsha_ctx* ctx, uint32_t n_chains, mirsha_chains** out);
 int mirsha_chains_create_hasher(mirsha_ctx* ctx, uint32_t n_chains, int hasher, mirsha_chains** out);
 int mirsha_chains_hasher(const mirsha_chains* chains);
+int mirsha_chains_pair_launches(const mirsha_chains* chains, uint64_t* out);
 void mirsha_chains_destroy(mirsha_chains* chains);
 int mirsha_chains_absorb(mirsha_ctx* ctx, mirsha_chains* chains, const uint8_t* digests, const uint32_t* chain_of,
                          uint32_t m);

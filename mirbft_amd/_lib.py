@@ -171,6 +171,7 @@ SIGNATURES = {
     "mirsha_chains_create": (c_int, [c_void_p, c_uint32, POINTER(c_void_p)]),
     "mirsha_chains_create_hasher": (c_int, [c_void_p, c_uint32, c_int, POINTER(c_void_p)]),
     "mirsha_chains_hasher": (c_int, [c_void_p]),
+    "mirsha_chains_pair_launches": (c_int, [c_void_p, _u64p]),
     "mirsha_chains_destroy": (None, [c_void_p]),
     "mirsha_chains_absorb": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32]),
     "mirsha_chains_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),

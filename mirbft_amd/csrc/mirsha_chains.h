@@ -1,6 +1,8 @@
 // mirsha_chains.h — what the checkpoint-chain units share (mirsha_chains.hip:
 // the SHA-256 kernels and every mirsha_chains_* entry point;
-// mirsha_sha512_chains.hip: the SHA-512/256 kernels).  Not part of the C-ABI.
+// mirsha_sha512_chains.hip: the SHA-512/256 kernels; mirsha_sha512_chains_pair.hip:
+// their producer/consumer pair forms and the route between the two).  Not part
+// of the C-ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,9 +22,13 @@ struct ChainKernels {
     void (*h0)(void* h);           // Hasher(): the h words of one chain
     // One lane per active chain act[k] with entries ent[efirst[k] ..
     // efirst[k + 1]); checkpoint values to 32-byte rows of `out` (NULL when no
-    // entry is a checkpoint).
+    // entry is a checkpoint).  `variant` (the context's, mirsha_ctx_set_variant)
+    // and `pair_launches` (the chains object's counter, may be NULL) are for a
+    // hasher whose kernels have more than one form (mirsha_sha512_chains.h);
+    // the SHA-256 row ignores both.  One kernel either way.
     hipError_t (*commit)(const uint8_t* digests, const uint32_t* ent, const uint32_t* act, const uint32_t* efirst,
-                         uint32_t n_active, void* h, void* pend, uint64_t* cnt, uint8_t* out, hipStream_t s);
+                         uint32_t n_active, void* h, void* pend, uint64_t* cnt, uint8_t* out, int variant,
+                         hipStream_t s, uint64_t* pair_launches);
     // mirsha_chains_absorb's grouped writes pos[afirst[k] .. afirst[k + 1]).
     // NULL: they run as a commit programme without checkpoints.
     hipError_t (*absorb)(const uint8_t* digests, const uint32_t* pos, const uint32_t* act, const uint32_t* afirst,
@@ -37,11 +43,12 @@ struct ChainKernels {
     // Hasher(); a LAST segment stores the state it ends in to h / pend / cnt.
     // Checkpoint values go to 32-byte rows of `out` (16-byte aligned, device or
     // host-visible memory) with plain vector stores.  `prio`: the issue
-    // priority (0-3) the waves take at entry.
+    // priority (0-3) the waves take at entry.  `variant`, `pair_launches`: as
+    // commit's.
     hipError_t (*commit_seg)(const uint8_t* digests, const uint32_t* ent, const uint32_t* seg_chain,
                              const uint32_t* sfirst, const uint32_t* seg_flags, uint32_t n_seg, const void* h_in,
                              const void* pend_in, const uint64_t* cnt_in, void* h, void* pend, uint64_t* cnt,
-                             uint8_t* out, uint32_t prio, hipStream_t s);
+                             uint8_t* out, uint32_t prio, int variant, hipStream_t s, uint64_t* pair_launches);
 };
 const ChainKernels& chain_kernels(int hasher);
 

@@ -317,7 +317,7 @@ constexpr uint32_t chain_grid(uint32_t lanes) { return (lanes + kBlockThreads - 
 
 hipError_t launch_chains_commit(const uint8_t* digests, const uint32_t* ent, const uint32_t* act,
                                 const uint32_t* efirst, uint32_t n_active, void* h, void* pend, uint64_t* cnt,
-                                uint8_t* out, hipStream_t s) {
+                                uint8_t* out, int /*variant*/, hipStream_t s, uint64_t* /*pair_launches*/) {
     if (n_active == 0) return hipSuccess;
     launch_k(chains_commit_kernel, chain_grid(n_active), kBlockThreads, 0, s, digests, ent, act, efirst, n_active,
              static_cast<uint32_t*>(h), static_cast<uint32_t*>(pend), cnt, out);
@@ -349,7 +349,8 @@ hipError_t launch_chains_reset(const uint32_t* which, uint32_t k, void* h, uint6
 hipError_t launch_chains_commit_seg(const uint8_t* digests, const uint32_t* ent, const uint32_t* seg_chain,
                                     const uint32_t* sfirst, const uint32_t* seg_flags, uint32_t n_seg, const void* h_in,
                                     const void* pend_in, const uint64_t* cnt_in, void* h, void* pend, uint64_t* cnt,
-                                    uint8_t* out, uint32_t prio, hipStream_t s) {
+                                    uint8_t* out, uint32_t prio, int /*variant*/, hipStream_t s,
+                                    uint64_t* /*pair_launches*/) {
     if (n_seg == 0) return hipSuccess;
     launch_k(chains_commit_seg_kernel, chain_grid(n_seg), kBlockThreads, 0, s, digests, ent, seg_chain, sfirst,
              seg_flags, n_seg, static_cast<const uint32_t*>(h_in), static_cast<const uint32_t*>(pend_in), cnt_in,
@@ -446,7 +447,8 @@ int chains_commit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
     if (int r = timed_launch(c, 1, [&] {
             return mirsha::chain_kernels(ch->hasher).commit(d_dig, d_plan + o_ent, d_plan, d_plan + o_first, na,
                                                             ch->d_h.p, ch->d_pend.p, ch->d_cnt.as<uint64_t>(),
-                                                            ch->d_out.as<uint8_t>(), c->stream);
+                                                            ch->d_out.as<uint8_t>(), c->variant, c->stream,
+                                                            &ch->pair_launches);
         }))
         return r;
     if (values) HIP_TRY(c, hipMemcpyAsync(values_out, ch->d_out.p, 32ull * values, hipMemcpyDeviceToHost, c->stream));
@@ -509,7 +511,8 @@ int commit_submit(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digests, bool
                                    reinterpret_cast<const uint32_t*>(dv), reinterpret_cast<const uint32_t*>(dv + o_first),
                                    reinterpret_cast<const uint32_t*>(dv + o_flags), t.n_seg, state_in[0], state_in[1],
                                    reinterpret_cast<const uint64_t*>(state_in[2]), ch->d_h.p, ch->d_pend.p,
-                                   ch->d_cnt.as<uint64_t>(), rows, commit_seg_prio(), q);
+                                   ch->d_cnt.as<uint64_t>(), rows, commit_seg_prio(), c->variant, q,
+                                   &ch->pair_launches);
         },
         n_values_out, ticket_out);
 }
@@ -560,6 +563,12 @@ int mirsha_chains_create(mirsha_ctx* c, uint32_t n, mirsha_chains** out) {
 }
 
 int mirsha_chains_hasher(const mirsha_chains* ch) { return ch ? ch->hasher : MIRSHA_EINVAL; }
+
+int mirsha_chains_pair_launches(const mirsha_chains* ch, uint64_t* out) {
+    if (!ch || !out) return MIRSHA_EINVAL;
+    *out = ch->pair_launches;
+    return MIRSHA_OK;
+}
 
 void mirsha_chains_destroy(mirsha_chains* ch) {
     if (!ch) return;
@@ -614,7 +623,8 @@ int mirsha_chains_absorb(mirsha_ctx* c, mirsha_chains* ch, const uint8_t* digest
             uint64_t* cnt = ch->d_cnt.as<uint64_t>();
             if (kern.absorb) return kern.absorb(dig, d_pos, d_act, d_afirst, na, ch->d_h.p, ch->d_pend.p, cnt, c->stream);
             // a commit programme without checkpoints: pos = the entries
-            return kern.commit(dig, d_pos, d_act, d_afirst, na, ch->d_h.p, ch->d_pend.p, cnt, nullptr, c->stream);
+            return kern.commit(dig, d_pos, d_act, d_afirst, na, ch->d_h.p, ch->d_pend.p, cnt, nullptr, c->variant,
+                               c->stream, &ch->pair_launches);
         }))
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // host vectors above feed async copies

@@ -44,6 +44,9 @@
 //                       launches and the routed launchers that choose between
 //                       them and the one-lane kernels (mirsha_sha512_pair.h;
 //                       hasher_launch_* below, plan_kernels)
+//   mirsha_sha512_chains_pair.hip  the pair forms of its chains' commit
+//                       kernels and their routed launchers
+//                       (mirsha_sha512_chains.h; chain_kernels)
 //
 // Every entry point returns digests in ORIGIN order (processor.go:139 indexes
 // Digests[i] by the request's position), unlike ProcessorWorkPool's
@@ -323,6 +326,10 @@ struct mirsha_chains {
     std::vector<uint32_t> plan;
     DevBuf d_plan;
     RingOwner ring;  // mirsha_chains_commit_submit*
+    // Commit launches (calls and tickets, absorb included) that took the
+    // SHA-512/256 pair kernels (mirsha_chains_pair_launches); counted where a
+    // launch is queued.  Stays 0 for SHA-256 chains.
+    uint64_t pair_launches = 0;
 };
 
 // Streaming hash states (see mirsha.h, mirsha_streams_create).

@@ -14,8 +14,9 @@
 // the 80 rounds from those words.  The split itself is sha512_pair.h (proved on
 // the CPU); the loaders are sha512_lanes.h, as in the one-lane kernels.
 //
-// Hand-over: groups of 16 rounds through a ring of two LDS slots, the producer
-// one group ahead, one workgroup barrier a group.  __syncthreads() is the only
+// Hand-over: groups of 16 rounds through a ring of two LDS slots
+// (sha512_pair_ring.h, shared with the chains' pair kernels), the producer one
+// group ahead, one workgroup barrier a group.  __syncthreads() is the only
 // synchronisation: no spinning, no atomics, nothing between workgroups.  Both
 // waves execute the same number of barriers on every input: every barrier
 // stands outside the producer / consumer branch, and the block loop's trip
@@ -35,43 +36,9 @@
 #include "mirsha_sha512_plan.h"
 #include "sha512_lanes.h"
 #include "sha512_pair.h"
+#include "sha512_pair_ring.h"
 
 namespace mirsha {
-
-// Wave 0 produces, wave 1 consumes; 64 messages or lists a workgroup.
-constexpr uint32_t kSha512PairThreads = 128;
-
-struct Sha512PairRing {
-    // [slot][pair of KW words][lane]: 16 bytes a lane, consecutive lanes
-    // consecutive, so every b128 access is conflict-free (as PairRing).
-    ulonglong2 kw[2][sha512::kPairGroupWords / 2][64];
-    // The walked loop's hand-over of "is there another block" (lists with
-    // nulls): per lane, and for the whole group of 64.  [block & 1].
-    uint32_t live[2][64];
-    uint32_t more[2];
-};
-static_assert(sizeof(Sha512PairRing) <= 65536u, "static LDS only");
-
-// One group of the schedule into a ring slot.
-template <int G>
-__device__ __forceinline__ void put_group(uint64_t w[16], ulonglong2 (*slot)[64], uint32_t lane) {
-    uint64_t kw[16];
-    sha512::produce_group<G>(w, kw);
-#pragma unroll
-    for (int q = 0; q < 8; q++) slot[q][lane] = make_ulonglong2(kw[2 * q], kw[2 * q + 1]);
-}
-
-// 16 rounds from a ring slot.
-__device__ __forceinline__ void take_group(ulonglong2 (*slot)[64], uint32_t lane, uint64_t v[8]) {
-    uint64_t kw[16];
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-        const ulonglong2 x = slot[q][lane];
-        kw[2 * q] = x.x;
-        kw[2 * q + 1] = x.y;
-    }
-    sha512::consume_group(v, kw);
-}
 
 // ---- producer-side sources of block words ----------------------------------
 // block(blk, w) is called for blocks 0, 1, 2, ... in order and returns whether
@@ -236,9 +203,6 @@ __device__ __forceinline__ void sha512_pair_loop(Src& src, Sha512PairRing& ring,
         if (!producer) sha512::finish_block(st, v, live);
     }
 }
-
-// Wave-uniform, and known to be: the branches on it are scalar.
-__device__ __forceinline__ bool is_producer() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0; }
 
 // ---- kernels -----------------------------------------------------------------
 

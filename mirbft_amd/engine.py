@@ -977,6 +977,16 @@ class CheckpointChains(_StateObject):
             self._engine._check(h)
         return {v: k for k, v in HASHERS.items()}[h]
 
+    @property
+    def pair_launches(self) -> int:
+        """Commit launches of these chains (write, the commit calls and the
+        commit tickets) that took the SHA-512/256 producer/consumer pair
+        kernels, counted where they are queued (mirsha_chains_pair_launches).
+        Always 0 for "sha256" chains."""
+        n = ctypes.c_uint64(0)
+        self._engine._check(self._lib.mirsha_chains_pair_launches(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
     def write(self, digests, chain_of) -> None:
         d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
         c = np.ascontiguousarray(chain_of, dtype=np.uint32).reshape(-1)
@@ -999,21 +1009,22 @@ class CheckpointChains(_StateObject):
         if w.size:
             self._engine._check(self._lib.mirsha_chains_reset(self._engine.ctx, self.handle, _ptr(w), w.size))
 
-    def commit(self, digests, op_chain, op_digest) -> np.ndarray:
+    def commit(self, digests, op_chain, op_digest, out=None) -> np.ndarray:
         """One cycle's commit programme in ONE call (mirsha_chains_commit, the
         commit loop of processor.go:145-168): op i acts on chain op_chain[i];
         op_digest[i] is a row of ``digests`` to write, MIRSHA_NULL_INDEX (a
         null request: nothing) or MIRSHA_COMMIT_CHECKPOINT (Sum, then a fresh
-        hasher).  Returns the checkpoint values, (k, 32) uint8, in op order."""
+        hasher).  Returns the checkpoint values, (k, 32) uint8, in op order
+        (in ``out`` when one is given)."""
         d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
-        return self._commit(self._lib.mirsha_chains_commit, _ptr(d), d.shape[0], op_chain, op_digest)
+        return self._commit(self._lib.mirsha_chains_commit, _ptr(d), d.shape[0], op_chain, op_digest, out)
 
-    def commit_device(self, d_digests: int, n_digests: int, op_chain, op_digest) -> np.ndarray:
+    def commit_device(self, d_digests: int, n_digests: int, op_chain, op_digest, out=None) -> np.ndarray:
         """commit() with the digest table in device memory (a raw device
         address, 16-byte aligned; e.g. the output of ``hash_batch_device``).
         The ops stay host arrays and the values come back to the host."""
         return self._commit(self._lib.mirsha_chains_commit_device, int(d_digests) or None, int(n_digests), op_chain,
-                            op_digest)
+                            op_digest, out)
 
     def _commit(self, call, table, n_digests: int, op_chain, op_digest, *ring):
         """``ring``: (out, keep, CommitTicket) of a submission."""
