@@ -412,8 +412,14 @@ int mirsha_verify_digests_device(mirsha_ctx* ctx, const uint8_t* d_digests, cons
                                  uint32_t n, uint64_t* d_bits_out, uint32_t* d_count_out);
 
 /* All pointers are device pointers; asynchronous on the context stream.
- * Reads past arena_len return 0.  Any arena size: up to
- * MIRSHA_MAX_DEVICE_ARENA_BYTES one 32-bit buffer descriptor addresses it,
+ * d_off and d_len live on the device, so the library cannot reject a message
+ * that overhangs the arena as the host calls do; the loaders range-check
+ * instead: reads at or past arena_len rounded up to a multiple of 4 return 0;
+ * up to 3 bytes behind arena_len must be readable (loads are whole 32-bit
+ * words, and an overhanging message hashes those bytes as they are).  Any
+ * arena size: up to MIRSHA_MAX_DEVICE_ARENA_BYTES one 32-bit buffer descriptor
+ * addresses it, and there a message's off + len must stay below 2^32 (a block
+ * offset that crosses 2^32 wraps to the arena's start instead of reading 0);
  * beyond that (BASELINE config 5: ~123 GB per GPU in one launch) the loader
  * switches to 64-bit per-lane addresses.  order (may be NULL) lists message
  * indices in processing order, e.g. from mirsha_bucket_order (longest first:
@@ -424,7 +430,9 @@ int mirsha_hash_batch_device(mirsha_ctx* ctx, const uint8_t* d_arena, uint64_t a
                              const uint32_t* d_order, uint32_t n, uint8_t* d_digests_out);
 
 /* d_digests holds n_digests 32-byte digests (< 2^27; reads are range-checked,
- * an out-of-range index reads zeros).  n_entries = d_list_first[n_lists] (the
+ * an out-of-range index reads zeros: every index in [n_digests,
+ * MIRSHA_NULL_INDEX), whatever its value, contributes 32 zero bytes, where the
+ * host call rejects it).  n_entries = d_list_first[n_lists] (the
  * caller knows it; it sizes the library's scratch for lists that contain
  * MIRSHA_NULL_INDEX entries). */
 int mirsha_digest_lists_device(mirsha_ctx* ctx, const uint8_t* d_digests, uint32_t n_digests,

@@ -114,11 +114,15 @@ __device__ __forceinline__ uint32_t ld_u32(__amdgpu_buffer_rsrc_t rs, uint32_t o
     return __builtin_amdgcn_raw_buffer_load_b32(rs, live ? off : 0xFFFFFFF0u, 0, kNoMerge);
 }
 
-// Digest `id` through a range-checked descriptor: a dead slot (or an index
-// past n_digests) reads zeros instead of faulting, without a branch.
+// Digest `id` through a range-checked descriptor: a dead slot, and any index
+// at or past n_digests whatever its value, reads zeros instead of faulting,
+// without a branch.  The row offset is 32 bits, so the index is clamped to
+// kMaxListDigests ahead of the multiply: 32 * (2^27 - 1) = 0xFFFFFFE0 lies
+// outside every table (n_digests <= 2^27 - 1), where 32 * 2^27 would wrap to
+// row 0.  kNullIndex, when a caller passes it as live, clamps there too.
 __device__ __forceinline__ void load_digest(__amdgpu_buffer_rsrc_t rsrc, uint32_t id, bool live, uint4& x0,
                                             uint4& x1) {
-    const uint32_t o = live ? 32u * id : 0xFFFFFFE0u;
+    const uint32_t o = live ? 32u * min(id, kMaxListDigests) : 0xFFFFFFE0u;
     const auto a = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o, 0, 0);
     const auto b = __builtin_amdgcn_raw_buffer_load_b128(rsrc, o + 16u, 0, 0);
     x0 = make_uint4(a[0], a[1], a[2], a[3]);

@@ -65,7 +65,9 @@ hipError_t launch_msgs(const uint8_t* arena, uint64_t arena_len, const uint64_t*
                        const uint32_t* len, const uint32_t* order, uint32_t n, uint8_t* out,
                        int variant, hipStream_t s);
 // scratch: device buffer with at least first[n_lists] entries (null compaction).
-// Digest reads are range-checked against n_digests (out-of-range reads zeros).
+// Digest reads are range-checked against n_digests: any index in [n_digests,
+// kNullIndex) reads zeros, whatever its value (load_digest clamps the index to
+// kMaxListDigests ahead of the 32-bit row offset).
 constexpr uint32_t kMaxListDigests = (1u << 27) - 1u;
 // Index reads are range-checked against n_entries (= first[n_lists]).
 constexpr uint32_t kMaxListEntries = (1u << 30) - 1u;

@@ -385,8 +385,12 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
     const uint32_t max_l = wave_max(valid ? L : 0u);
     const uint32_t wave_nb = blocks_for_len(max_l);
 
-    // Bytes past arena_len inside the last dword are never part of a message
-    // (they are masked by the padding logic), so the range rounds up to 4.
+    // The range rounds up to 4: loads are whole dwords.  Bytes past arena_len
+    // inside the last dword are masked by the padding logic for a message that
+    // ends at or below arena_len; a message that overhangs arena_len (only the
+    // device call can pass one) hashes them as they are, and zeros from
+    // `records` onward (mirsha.h, mirsha_hash_batch_device).  The descriptor
+    // offsets are 32 bits: a message's off + len stays below 2^32.
     const uint64_t records = (arena_len + 3u) & ~3ull;
     const __amdgpu_buffer_rsrc_t rsrc =
         __builtin_amdgcn_make_buffer_rsrc((void*)arena, (short)0, (int)(uint32_t)records, 0x00020000);

@@ -117,8 +117,10 @@ __device__ __forceinline__ void keep_row(uint32_t row[8], const uint4& x0, const
 
 // Skips MIRSHA_NULL_INDEX entries (they contribute nothing), four index loads
 // at a time; then requests the rows.  Index loads are range-checked against
-// n_entries and row loads against n_digests (out of range reads zeros, as
-// hash_list does).  !live: no entry is read, every load takes a dead offset.
+// n_entries and row loads against n_digests (an index in [n_digests,
+// kNullIndex) reads zeros whatever its value: load_digest clamps it ahead of
+// the 32-bit row offset, as for hash_list).  !live: no entry is read, every
+// load takes a dead offset.
 // The row ids are kept by selects, never by a dynamic register index.
 __device__ __forceinline__ void fetch_rows(__amdgpu_buffer_rsrc_t drs, __amdgpu_buffer_rsrc_t irs, uint32_t& e,
                                            uint32_t e1, bool live, ListRows& r) {
