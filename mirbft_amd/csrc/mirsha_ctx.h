@@ -388,6 +388,10 @@ struct mirsha_pipeline {
     bool trace = false;
     std::vector<uint32_t> cidx, cfirst;      // compacted lists (no null entries)
     uint32_t uniform = 0;                    // B: identity lists of B entries (uniform_lists), else 0
+    // Every length given at creation equal: what the request launch may assume
+    // of each tile until the tile's own lengths and offsets say otherwise
+    // (mirsha_hints.h; packed requests, stride = length).  valid == 0: none.
+    mirsha::UniformHint hint{};
     std::vector<uint32_t> order;             // request processing order
     DevBuf d_cidx, d_cfirst, d_order;
 };
@@ -440,11 +444,11 @@ int timed_launch(mirsha_ctx* c, int which, F&& launch) {
 // by the launch's size and the context's variant, one kernel either way.
 inline hipError_t hasher_launch_msgs(const mirsha_ctx* c, const uint8_t* arena, uint64_t arena_len,
                                      const uint64_t* off, const uint32_t* len, const uint32_t* order, uint32_t n,
-                                     uint8_t* out, hipStream_t s) {
+                                     uint8_t* out, hipStream_t s, const mirsha::UniformHint* hint = nullptr) {
     if (c->hasher == MIRSHA_HASHER_SHA512_256)
         return mirsha::launch_sha512_msgs(arena, arena_len, off, len, order, n, out, c->variant, s,
                                           &c->sha512_pair_launches);
-    return mirsha::launch_msgs(arena, arena_len, off, len, order, n, out, c->variant, s);
+    return mirsha::launch_msgs(arena, arena_len, off, len, order, n, out, c->variant, s, hint);
 }
 inline hipError_t hasher_launch_lists(const mirsha_ctx* c, const uint8_t* digests, uint32_t n_digests,
                                       const uint32_t* idx, uint32_t n_entries, const uint32_t* first, uint32_t n_lists,

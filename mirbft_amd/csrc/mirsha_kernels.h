@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mirsha_hints.h"
+
 namespace mirsha {
 
 constexpr uint32_t kWavesPerBlock = 4;
@@ -61,9 +63,12 @@ struct LaunchEvents {
 };
 LaunchEvents& next_launch_events();
 
+// hint (optional): what the host knows of a uniform launch (mirsha_hints.h).
+// Only the full-occupancy LDS form reads it, and proves it per wave; every
+// other form, and a launch without one, runs as before.
 hipError_t launch_msgs(const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
                        const uint32_t* len, const uint32_t* order, uint32_t n, uint8_t* out,
-                       int variant, hipStream_t s);
+                       int variant, hipStream_t s, const UniformHint* hint = nullptr);
 // scratch: device buffer with at least first[n_lists] entries (null compaction).
 // Digest reads are range-checked against n_digests: any index in [n_digests,
 // kNullIndex) reads zeros, whatever its value (load_digest clamps the index to

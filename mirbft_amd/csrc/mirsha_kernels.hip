@@ -18,6 +18,7 @@
 // and the per-lane ds_read_b128 (16-lane groups) are bank-conflict free.
 #include <algorithm>
 #include <atomic>
+#include <cstddef>
 #include <cstdlib>
 #include <cstdio>
 #include <type_traits>
@@ -115,10 +116,12 @@ __device__ __forceinline__ void pad_words(uint32_t p, uint32_t L, bool last_bloc
 // words are scalar, one v_bitop3 per word.
 // kWords < 16: only the first kWords words (the final-block tail form keeps
 // the rest, and the bit length, as scalars).
-template <int kWords = 16>
+// kFirst: words kFirst .. kFirst + kWords - 1 (hash_tile_uniform pads a block
+// four words at a time).
+template <int kWords = 16, int kFirst = 0>
 __device__ __forceinline__ void pad_block_uniform(uint32_t w[16], uint32_t soff, uint32_t L, bool last) {
 #pragma unroll
-    for (int k = 0; k < kWords; k++) {
+    for (int k = kFirst; k < kFirst + kWords; k++) {
         const int32_t t = (int32_t)(L - (soff + 4u * k));  // message bytes left at word k
         const uint32_t sh = (uint32_t)t << 3;              // only used when 0 <= t <= 3
         uint32_t keep = t >= 4 ? 0xFFFFFFFFu : (t <= 0 ? 0u : ~(0xFFFFFFFFu >> sh));
@@ -353,8 +356,9 @@ __device__ __forceinline__ void block_prio(uint32_t fprio, uint32_t blk) {
 // stored), kTilePaused when it did not (st_io then holds the midstate after
 // block b1 - 1).  (A range that starts at or past the tile's end is never
 // passed: the fused launch skips such split-tile segments itself.)
+// kTail false: no tail form (the hinted kernel's fallback, sha256_msgs_kernel).
 constexpr uint32_t kTilePaused = 0, kTileDone = 1;
-template <bool kLds, bool kWide, bool kFused = false, bool kDma = false>
+template <bool kLds, bool kWide, bool kFused = false, bool kDma = false, bool kTail = true>
 __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena, uint64_t arena_len,
                                           const uint64_t* __restrict__ off, const uint32_t* __restrict__ len,
                                           const uint32_t* __restrict__ order, uint32_t n, uint8_t* __restrict__ out,
@@ -437,7 +441,7 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
         // Final-block tail form (compress_asm_tail) for uniform tiles whose
         // final block holds at most 16 message bytes; its scalars up front.
         const int32_t u_last = (int32_t)(min_l - 64u * (wave_nb - 1u));
-        const bool tail_ok = uni && u_last <= 16;
+        const bool tail_ok = kTail && uni && u_last <= 16;
         const TailWords tw = tail_words(u_last, min_l);
         uint32_t vo[4], sel[4];
 #pragma unroll
@@ -683,6 +687,155 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
     return kTileDone;
 }
 
+// The request kernels' argument block (one struct, so a field's offset in the
+// kernel's argument segment is its offsetof).
+struct MsgsArgs {
+    const uint8_t* arena;
+    uint64_t arena_len;
+    const uint64_t* off;
+    const uint32_t* len;
+    const uint32_t* order;  // NULL = identity
+    uint32_t n;
+    uint8_t* out;
+    UniformHint hint;  // valid == 0: none
+};
+// A dword of the kernel's argument segment, loaded where it is used.
+__device__ __forceinline__ uint32_t kernarg_u32(uint32_t byte_off) {
+    const auto* p = (const __attribute__((address_space(4))) uint32_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    return p[byte_off / 4u];
+}
+
+// progress_prio for a block index that is an SGPR already (a hinted tile's
+// loop counter): scalar compares, where progress_prio's saturating subtract
+// and readfirstlane are three VALU ops per block.
+__device__ __forceinline__ void progress_prio_uniform(uint32_t blk) {
+    static_assert(kPrioTop == 3, "progress_prio_uniform spells out priorities 3..0");
+    if (blk == 0u) __builtin_amdgcn_s_setprio(3);
+    else if (blk == 1u) __builtin_amdgcn_s_setprio(2);
+    else if (blk == 2u) __builtin_amdgcn_s_setprio(1);
+    else __builtin_amdgcn_s_setprio(0);
+}
+
+// A hinted tile (UniformHint, mirsha_hints.h): the launch's messages are said
+// to be h.len bytes each, h.stride bytes apart and 4-byte aligned.  The wave
+// proves that of its own tile from the lengths and offsets it loaded -- two
+// ballots and scalar compares -- and, when the proof holds, hashes the tile
+// with everything hash_tile finds out per wave taken from the hint instead:
+// no wave_max / wave_min, no 64-bit reach per lane, the loader addresses by a
+// multiply-add instead of four shuffles, plain byte swaps (no fifth dword,
+// no per-chunk selector), and the block count, the padding test and the
+// tail form's scalars as kernel arguments.  A tail-form final block's 16
+// bytes are each lane's own 128-bit load, issued behind the last staged
+// block's read-back, with no second pass through LDS.  Returns false, with
+// nothing written, when the proof fails: the caller then runs hash_tile.
+// The proof, for the tile's valid lanes i (lane 0 is always valid):
+//   len == h.len;  off == off[lane 0] + i * h.stride (64 bits);
+//   off[lane 0] and h.stride multiples of 4;
+//   off[last valid lane] + h.reach <= records (every load in range, so the
+//   descriptor's 32-bit offsets hold and no access is zeroed by the range
+//   check; the hint's own scalars come from make_uniform_hint alone).
+__device__ __forceinline__ bool hash_tile_uniform(const uint8_t* __restrict__ arena, uint64_t arena_len,
+                                                  const uint64_t* __restrict__ off, const uint32_t* __restrict__ len,
+                                                  const uint32_t* __restrict__ order, uint32_t n,
+                                                  uint8_t* __restrict__ out, uint4* my, uint32_t t, uint32_t lane,
+                                                  const UniformHint& h) {
+    __builtin_amdgcn_s_setprio(3);  // (hash_tile: the prologue at the highest issue priority)
+    t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);  // wave-uniform: the proof's compares stay scalar
+    const uint32_t slot = t * 64u + lane;
+    const bool valid = slot < n;
+    const uint32_t slot_c = valid ? slot : n - 1u;  // unconditional loads, as in hash_tile
+    const uint32_t msg = order ? order[slot_c] : slot_c;
+    const uint32_t L_ = len[msg];
+    const uint64_t o_ = off[msg];
+    const uint32_t o0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o_);
+    const uint32_t o0_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o_ >> 32));
+    // (| and &, not || and &&: one compare chain, no exec-mask branches)
+    const bool odd = valid & ((L_ != h.len) | (o_ != (((uint64_t)o0_hi << 32 | o0) + (uint64_t)lane * h.stride)));
+    // The narrow form's arena is below 2^32 bytes (launch_msgs), so the reach
+    // test is 32-bit scalar compares on a 64-bit sum that cannot wrap.
+    const uint32_t records = (uint32_t)((arena_len + 3u) & ~3ull);
+    const uint32_t last = min(64u, n - t * 64u) - 1u;  // the tile's last valid lane
+    const uint64_t end = (uint64_t)o0 + (uint64_t)last * h.stride + h.reach;
+    const bool proven = (__builtin_amdgcn_ballot_w64(odd) == 0) & (((o0 | h.stride) & 3u) == 0u) & (o0_hi == 0u) &
+                        ((uint32_t)(end >> 32) == 0u) & ((uint32_t)end <= records);
+    if (!proven) return false;
+
+    const __amdgpu_buffer_rsrc_t rsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)arena, (short)0, (int)records, 0x00020000);
+    // Loader roles as in hash_tile: quarter q of messages 16 j + lane / 4.
+    const uint32_t q = lane & 3u, m = lane >> 2;
+    const uint32_t vbase = o0 + m * h.stride + 16u * q;
+    const uint32_t wslot = lds_slot(m, q);  // lds_slot(16 j + m, q) = wslot + 64 j
+    uint32_t st[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) st[i] = kH0[i];
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 tv = {0u, 0u, 0u, 0u};
+    const uint32_t vtail = o0 + lane * h.stride + 64u * h.loop_nb;  // this lane's own final block
+    if (h.tail_bytes && h.loop_nb == 0u) tv = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vtail, 0, 0);
+    for (uint32_t blk = 0; blk < h.loop_nb; blk++) {
+        const uint32_t soff = 64u * blk;
+        u32x4 v[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            v[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vbase + 16u * (uint32_t)j * h.stride, soff, 0);
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            my[wslot + 64u * (uint32_t)j] = make_uint4(__builtin_bswap32(v[j][0]), __builtin_bswap32(v[j][1]),
+                                                       __builtin_bswap32(v[j][2]), __builtin_bswap32(v[j][3]));
+        uint32_t w[16];
+        wave_lds_handoff();
+        tile_read_words(my, lane, w);
+        wave_lds_handoff();
+        // (last_block_opaque: no peeled last iteration, see there)
+        if (h.tail_bytes && last_block_opaque(h.loop_nb, blk)) tv = __builtin_amdgcn_raw_buffer_load_b128(rsrc, vtail, 0, 0);
+        if (soff + 64u > h.len) {  // four words at a time: 8 mask SGPRs live, not 32
+            const bool lastb = last_block_opaque(h.nb, blk);
+            pad_block_uniform<4, 0>(w, soff, h.len, lastb);
+            __builtin_amdgcn_sched_barrier(0);
+            pad_block_uniform<4, 4>(w, soff, h.len, lastb);
+            __builtin_amdgcn_sched_barrier(0);
+            pad_block_uniform<4, 8>(w, soff, h.len, lastb);
+            __builtin_amdgcn_sched_barrier(0);
+            pad_block_uniform<4, 12>(w, soff, h.len, lastb);
+        }
+        progress_prio_uniform(blk);
+        compress_asm(st, w);  // (idle lanes too: their state is never stored)
+    }
+    if (h.tail) {
+        uint32_t w[16];
+        w[0] = __builtin_bswap32(tv[0]); w[1] = __builtin_bswap32(tv[1]);
+        w[2] = __builtin_bswap32(tv[2]); w[3] = __builtin_bswap32(tv[3]);
+        // The tail form's masks and scalars are read from the argument block
+        // here, not as formal arguments: those are loaded at kernel entry and
+        // would hold 19 SGPRs across the block loop (the compiler's budget at
+        // 8 waves per SIMD is 80, and hash_tile in the same kernel needs 77).
+        auto arg = [&](size_t field) { return kernarg_u32((uint32_t)(offsetof(MsgsArgs, hint) + field)); };
+        if (h.tail_pad) {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                w[k] = (w[k] & arg(offsetof(UniformHint, keep) + 4u * k)) | arg(offsetof(UniformHint, mark) + 4u * k);
+        }
+        constexpr size_t kTw = offsetof(UniformHint, tw);
+        const TailWords tw = {arg(kTw + offsetof(HintTail, kw4)),  arg(kTw + offsetof(HintTail, kw14)),
+                              arg(kTw + offsetof(HintTail, kw15)), arg(kTw + offsetof(HintTail, c4)),
+                              arg(kTw + offsetof(HintTail, c14)),  arg(kTw + offsetof(HintTail, c15)),
+                              arg(kTw + offsetof(HintTail, cs16)), arg(kTw + offsetof(HintTail, cs17)),
+                              arg(kTw + offsetof(HintTail, cs19)), arg(kTw + offsetof(HintTail, cs29)),
+                              arg(kTw + offsetof(HintTail, cs30))};
+        progress_prio_uniform(h.nb - 1u);
+        compress_asm_tail(st, w, tw);
+    }
+    // The digest table and the count from the argument block again (as the
+    // tail scalars above), so that no SGPR holds them across the blocks.
+    const uint32_t n_end = kernarg_u32((uint32_t)offsetof(MsgsArgs, n));
+    uint8_t* const out_end = reinterpret_cast<uint8_t*>(
+        (uint64_t)kernarg_u32((uint32_t)offsetof(MsgsArgs, out)) |
+        (uint64_t)kernarg_u32((uint32_t)offsetof(MsgsArgs, out) + 4u) << 32);
+    if (slot < n_end) tile_store<false, true>(out_end, n_end, msg, st);
+    return true;
+}
+
 // One wave per workgroup: a workgroup's slot and LDS are released only when
 // ALL its waves have finished, and the SIMD arbiter's age order finishes a
 // workgroup's waves (one per SIMD) far apart, so 4-wave workgroups left SIMDs
@@ -690,17 +843,25 @@ __device__ __forceinline__ uint32_t hash_tile(const uint8_t* __restrict__ arena,
 // the register budget to 64 VGPRs (the wide form keeps 6: 80 VGPRs, no spill).
 constexpr uint32_t kMsgWaves = 1;
 constexpr uint32_t kMsgOcc = 8, kTileSlots = 256;
-template <bool kLds, bool kWide = false>
-__global__ __launch_bounds__(64 * kMsgWaves, kWide ? 6 : kMsgOcc) void sha256_msgs_kernel(
-    const uint8_t* __restrict__ arena, uint64_t arena_len, const uint64_t* __restrict__ off,
-    const uint32_t* __restrict__ len, const uint32_t* __restrict__ order, uint32_t n,
-    uint8_t* __restrict__ out) {
+// kHint (the LDS loader's narrow form only): the launch carries a UniformHint;
+// a wave whose tile proves it takes hash_tile_uniform, any other hash_tile
+// (the branch is wave-uniform).  That hash_tile is the unhinted kernel's
+// without the tail form (kTail false: a uniform tile's final block goes
+// through the block loop like any other, same digests): with both tail
+// rounds in one kernel the allocator spilled 9 SGPRs and 8 bytes of scratch,
+// and only tiles that fail the proof run it.
+template <bool kLds, bool kWide = false, bool kHint = false>
+__global__ __launch_bounds__(64 * kMsgWaves, kWide ? 6 : kMsgOcc) void sha256_msgs_kernel(MsgsArgs a) {
     __shared__ uint4 tile[kMsgWaves][kTileSlots];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = threadIdx.x >> 6;
     const uint32_t t = blockIdx.x * kMsgWaves + wv;
-    if (t * 64u >= n) return;  // whole wave idle (wave-uniform)
-    hash_tile<kLds, kWide>(arena, arena_len, off, len, order, n, out, tile[wv], t, lane);
+    if (t * 64u >= a.n) return;  // whole wave idle (wave-uniform)
+    if constexpr (kHint) {
+        static_assert(kLds && !kWide, "hinted tiles: the narrow LDS loader only");
+        if (hash_tile_uniform(a.arena, a.arena_len, a.off, a.len, a.order, a.n, a.out, tile[wv], t, lane, a.hint)) return;
+    }
+    hash_tile<kLds, kWide, false, false, !kHint>(a.arena, a.arena_len, a.off, a.len, a.order, a.n, a.out, tile[wv], t, lane);
 }
 
 // CU-block form of the request kernel, for launches of 1,025 to 4,096 tiles
@@ -1912,13 +2073,14 @@ hipError_t dyn_lds_attr(const void* fn, DynLdsKernel form, uint32_t bytes) {
 
 hipError_t launch_msgs(const uint8_t* arena, uint64_t arena_len, const uint64_t* off,
                        const uint32_t* len, const uint32_t* order, uint32_t n, uint8_t* out,
-                       int variant, hipStream_t s) {
+                       int variant, hipStream_t s, const UniformHint* hint) {
+    const MsgsArgs a{arena, arena_len, off, len, order, n, out, (hint && hint->valid) ? *hint : UniformHint{}};
     if (n == 0) return hipSuccess;
     const uint32_t tiles = (n + 63u) / 64u;
     const uint32_t grid = (tiles + kWavesPerBlock - 1u) / kWavesPerBlock;
     const uint32_t mgrid = (tiles + kMsgWaves - 1u) / kMsgWaves;
     if (arena_len > kMaxBufferArena || n >= kMaxBufferMsgs) {  // 64-bit addressing (LDS loader)
-        launch_k(sha256_msgs_kernel<true, true>, mgrid, 64 * kMsgWaves, 0, s, arena, arena_len, off, len, order, n, out);
+        launch_k(sha256_msgs_kernel<true, true>, mgrid, 64 * kMsgWaves, 0, s, a);
         return hipGetLastError();
     }
     if (variant == kVariantPair || (variant == kVariantLds && tiles <= pair_max_groups())) {
@@ -1939,9 +2101,11 @@ hipError_t launch_msgs(const uint8_t* arena, uint64_t arena_len, const uint64_t*
         return hipGetLastError();
     }
     if (variant == kVariantDirect)
-        launch_k(sha256_msgs_kernel<false>, mgrid, 64 * kMsgWaves, 0, s, arena, arena_len, off, len, order, n, out);
+        launch_k(sha256_msgs_kernel<false>, mgrid, 64 * kMsgWaves, 0, s, a);
+    else if (a.hint.valid)
+        launch_k(sha256_msgs_kernel<true, false, true>, mgrid, 64 * kMsgWaves, 0, s, a);
     else
-        launch_k(sha256_msgs_kernel<true>, mgrid, 64 * kMsgWaves, 0, s, arena, arena_len, off, len, order, n, out);
+        launch_k(sha256_msgs_kernel<true>, mgrid, 64 * kMsgWaves, 0, s, a);
     return hipGetLastError();
 }
 

@@ -55,6 +55,12 @@ int pipeline_build(mirsha_ctx* c, mirsha_pipeline* p, uint32_t n_req, const uint
     }
     p->n_entries = (uint32_t)p->cidx.size();
     p->uniform = uniform_lists(p->cidx, p->cfirst);
+    // The request launch's hint: one length for every request (BASELINE
+    // configs 2 and 3, the Go binding's packed arenas).  The lengths and
+    // offsets of a run are the device's; the kernel proves the hint per tile.
+    p->hint = mirsha::UniformHint{};
+    if (len && n_req && std::all_of(len, len + n_req, [&](uint32_t l) { return l == len[0]; }))
+        p->hint = mirsha::make_uniform_hint(len[0], len[0]);
     // Processing order: listed requests first, then longest-first by block
     // count (length bucketing inside a wave), stable.
     p->order.resize(n_req);
@@ -97,7 +103,7 @@ const PlanKernels kPlanSha256 = {
     [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_arena, uint64_t arena_len, const uint64_t* d_off,
        const uint32_t* d_len, uint8_t* d_req_out) {
         return mirsha::launch_msgs(d_arena, arena_len, d_off, d_len, p->d_order.as<uint32_t>(), p->n_req, d_req_out,
-                                   c->variant, c->stream);
+                                   c->variant, c->stream, &p->hint);
     },
     [](const mirsha_ctx* c, const mirsha_pipeline* p, const uint8_t* d_digests, uint8_t* d_list_out) {
         if ((p->n_lists + 63u) / 64u <= mirsha::pair_max_groups())  // few long chains: producer/consumer pairs

@@ -129,25 +129,40 @@ struct MetaLayout {
 
 // Metadata of n messages into the pinned block: offsets rebased by `shift`,
 // lengths, and whether the block counts differ (a bucket order is needed).
-// One parallel pass.
-bool meta_fill(const uint64_t* off, const uint32_t* len, uint32_t n, uint64_t shift, uint8_t* h, const MetaLayout& L) {
-    std::atomic<uint32_t> lo_b{UINT32_MAX}, hi_b{0};
+// One parallel pass.  *hint: the request launch's hint when every length is
+// the same (stride from the first two offsets; the kernel proves it per tile).
+bool meta_fill(const uint64_t* off, const uint32_t* len, uint32_t n, uint64_t shift, uint8_t* h, const MetaLayout& L,
+               mirsha::UniformHint* hint) {
+    std::atomic<uint32_t> lo_b{UINT32_MAX}, hi_b{0}, lo_l{UINT32_MAX}, hi_l{0};
     uint64_t* ho = reinterpret_cast<uint64_t*>(h + L.off);
     uint32_t* hl = reinterpret_cast<uint32_t*>(h + L.len);
     mirsha::host::parallel_for(n, mirsha::host::threads_for(12ull * n, n), [&](uint32_t a, uint32_t b) {
-        uint32_t lo = UINT32_MAX, hi = 0;
+        uint32_t lo = UINT32_MAX, hi = 0, lol = UINT32_MAX, hil = 0;
         for (uint32_t i = a; i < b; i++) {
             ho[i] = off[i] - shift;
             hl[i] = len[i];
             const uint32_t k = host_blocks(len[i]);
             lo = std::min(lo, k);
             hi = std::max(hi, k);
+            lol = std::min(lol, len[i]);
+            hil = std::max(hil, len[i]);
         }
-        uint32_t cur = lo_b.load();
-        while (lo < cur && !lo_b.compare_exchange_weak(cur, lo)) {}
-        cur = hi_b.load();
-        while (hi > cur && !hi_b.compare_exchange_weak(cur, hi)) {}
+        auto lower = [](std::atomic<uint32_t>& a, uint32_t v) {
+            uint32_t cur = a.load();
+            while (v < cur && !a.compare_exchange_weak(cur, v)) {}
+        };
+        auto raise = [](std::atomic<uint32_t>& a, uint32_t v) {
+            uint32_t cur = a.load();
+            while (v > cur && !a.compare_exchange_weak(cur, v)) {}
+        };
+        lower(lo_b, lo);
+        raise(hi_b, hi);
+        lower(lo_l, lol);
+        raise(hi_l, hil);
     });
+    *hint = mirsha::UniformHint{};
+    if (n && lo_l.load() == hi_l.load())
+        *hint = mirsha::make_uniform_hint(len[0], n > 1 ? off[1] - off[0] : (uint64_t)len[0]);
     return n && lo_b.load() != hi_b.load();
 }
 
@@ -543,7 +558,8 @@ int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const ui
     HIP_TRY(c, c->h_meta.ensure(L.end));
     HIP_TRY(c, c->d_meta.ensure(L.end));
     uint8_t* h = c->h_meta.as<uint8_t>();
-    const bool ordered = meta_fill(off, len, n, shift, h, L);
+    mirsha::UniformHint hint;
+    const bool ordered = meta_fill(off, len, n, shift, h, L, &hint);
     if (ordered) bucket_order(len, n, reinterpret_cast<uint32_t*>(h + L.order));
     if (entries) pmemcpy(h + L.idx, idx, 4ull * entries);
     if (n_lists) pmemcpy(h + L.first, first, 4ull * (n_lists + 1));
@@ -568,7 +584,7 @@ int run_staged(mirsha_ctx* c, const ArenaSrc& src, const uint64_t* off, const ui
                 return hasher_launch_msgs(c, d_arena, src.total, reinterpret_cast<const uint64_t*>(dm + L.off),
                                           reinterpret_cast<const uint32_t*>(dm + L.len),
                                           ordered ? reinterpret_cast<const uint32_t*>(dm + L.order) : nullptr, n,
-                                          d_req, c->stream);
+                                          d_req, c->stream, &hint);
             }))
             return rc;
     }
